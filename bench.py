@@ -10,22 +10,30 @@ global batch 65,536 (8,192 per GPU at 8 GPUs), Adam lr 1e-3.
 A "step" = fused fwd+loss+bwd kernel (+ the factored layer-0 expansion), tower-grad
 reduction, (RCCL gradient exchange when N > 1), dense Adam -- the whole optimizer
 step of scripts/train_neumf.py:111-115, captured into hipGraphs and replayed.
-The timed region is whole epochs (--steps rounded up): every epoch in it is a
-fresh epoch of the reference loop -- new negatives (NCFData.ng_sample, bit-exact;
+The timed region is exactly --steps steps after a warm-up of whole epochs; every
+epoch it enters is a fresh epoch of the reference loop -- new negatives (ng_sample, bit-exact;
 the parallel host sampler, prefetched while the previous epoch trains) and a new
 DataLoader permutation (bit-exact torch.randperm, on the device), packed,
 shuffled and grouped on the device (ncf_amd.pipeline).  The data set itself is
 resident in HBM before the timed region.  The global batch is the reference's
-batch size at every N (strong scaling); value = rows of the timed epochs /
-max-over-ranks time.  At N > 1 `weak_scaling` also times the per-GPU batch held
-at the single-GPU size.
+batch size at every N (strong scaling); value = rows of the timed steps /
+max-over-ranks time.  A plain run does that and prints the headline line;
+--dump-outputs DIR also writes what the last timed steps hand their caller as
+DIR/<name>.npy, computed once more from the seeded model so that it is the same in
+every run: the parameters after the first two of those steps and the loss of each of
+up to 64 of them.  The inputs are seeded, but the trained state itself depends on
+the order in which the scatter's float atomics happened to add (8 steps are enough
+for single weights to differ by 5e-3 of their range).  Two builds can be compared
+output for output.
 
-Also reported: `e2e` -- Trainer.fit (the scripts' loop: epochs + metrics() per
-epoch) at the same config, rows per epoch / epoch wall time; `cpu_baseline` -- the
-oracle (reference model restated on torch CPU ops) on the host cores, in a child
-process.
+With --full also reported: the `frozen_epoch` and `sustained` rates, per-kernel
+timings and rooflines, HR@10 / NDCG@10; at N > 1 `weak_scaling` (the per-GPU batch
+held at the single-GPU size); `e2e` -- Trainer.fit (the scripts' loop: epochs +
+metrics() per epoch) at the same config, rows per epoch / epoch wall time;
+`cpu_baseline` -- the oracle (reference model restated on torch CPU ops) on the
+host cores, in a child process.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 either under
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full]; for N > 1 either under
 torch.distributed.run (one process per GPU, RCCL) or directly, in which case the
 script spawns its N ranks itself before any GPU call.
 """
@@ -591,16 +599,49 @@ def restore_state(eng, snap):
     torch.cuda.synchronize(eng.device)
 
 
-def measure(cfg, ds, train, world, rank, dev, group, global_batch, steps, warmup, use_graph, whole_epochs=True):
-    """Warm-up, then whole fresh epochs timed (>= `steps` optimizer steps, rounded up
-    to whole epochs of `global_batch`-row global batches: every epoch in the timed
-    region draws new negatives and a new permutation), then the same number of steps
-    on the last epoch stream reused (`frozen`).  Max over ranks, barrier +
-    synchronize on both sides of each timed region.  whole_epochs=False (--profile-run:
-    rocprofv3 passes serialise every launch): exactly `warmup` and `steps` steps."""
+DUMP_BYTES = 64 * 2 ** 20  # --dump-outputs: at most this much in all
+DUMP_PARAM_STEPS, DUMP_LOSS_STEPS = 2, 64  # --dump-outputs: steps replayed from the seeded model (measure)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each tensor of `arrays` as <dirname>/<name>.npy (float32, its own
+    shape).  Above DUMP_BYTES in all (headers counted), every array of more than 4096
+    elements is cut to the same fraction of its elements: a fixed sample (seed 0,
+    ascending flat indices), written flat."""
+    os.makedirs(dirname, exist_ok=True)
+    # a file is its 128-byte header and 4 bytes per element; arrays of at most 4096
+    # elements stay whole, the others share what those leave of the budget
+    small = sum(128 + 4 * a.numel() for a in arrays.values() if a.numel() <= 4096)
+    large = sum(4 * a.numel() for a in arrays.values() if a.numel() > 4096)
+    room = DUMP_BYTES - small - 128 * sum(1 for a in arrays.values() if a.numel() > 4096)
+    if room < 0:
+        raise ValueError(f"--dump-outputs: {len(arrays)} arrays do not fit {DUMP_BYTES} bytes")
+    frac = min(1.0, room / max(1, large))
+    rng = np.random.default_rng(0)
+    for name, a in arrays.items():
+        a = a.detach()
+        if frac < 1.0 and a.numel() > 4096:
+            idx = np.sort(rng.choice(a.numel(), int(a.numel() * frac), replace=False))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(dirname, name + ".npy"), a.float().cpu().numpy())
+
+
+def measure(cfg, ds, train, world, rank, dev, group, global_batch, steps, warmup, use_graph, whole_epochs=True,
+            full=True, dump_dir=None):
+    """Warm-up, then exactly `steps` optimizer steps timed on `global_batch`-row global
+    batches: every epoch the timed region enters draws new negatives and a new
+    permutation.  `dump_dir`: the last timed steps are then run once more from the seeded
+    state and rank 0 writes what they hand their caller (the model's parameters after
+    DUMP_PARAM_STEPS of them, the loss of each of DUMP_LOSS_STEPS; dump_outputs), and the
+    trained state is put back.  `full`:
+    then the same number of steps on the last epoch stream reused (`frozen`) and the
+    `sustained` epochs.  Max over ranks, barrier + synchronize on both sides of each
+    timed region.  The warm-up is whole epochs; whole_epochs=False (--profile-run:
+    rocprofv3 passes serialise every launch): exactly `warmup` steps."""
     eng, model, pipe = setup_engine(cfg, ds, train, world, rank, dev, group, global_batch)
     nb = eng.num_batches
     n_rows = eng.n_total
+    snap_seed = snapshot_state(eng) if dump_dir is not None else None  # the seeded model, no step taken
     # warm-up: whole epochs, at least `warmup` steps and, with whole epochs, at least
     # WARM_S seconds -- the first process on a fresh box ran its first timed C3 epoch
     # at 61 us/step after one or two warm-up epochs (~10 ms) against 57 in the next
@@ -614,21 +655,29 @@ def measure(cfg, ds, train, world, rank, dev, group, global_batch, steps, warmup
     # every rank must run the same number of steps (each step is a collective at N > 1):
     # another epoch while any rank is short of WARM_S.  Those extra epochs only warm the
     # device: the trained state goes back to the one the requested warm-up left (the
-    # quality figures stay those of a few epochs of training, as in the reference's runs)
+    # quality figures stay those of a few epochs of training, as in the reference's runs).
+    # They replay the current epoch stream (no new negatives or permutation drawn): how
+    # many of them a run needs depends on the clock, and the timed steps' inputs must not
+    # depend on it
     snap0 = None
     extra = 0
     while whole_epochs and _max_over_ranks(float(time.perf_counter() - t_w < WARM_S), group, dev) > 0:
         if snap0 is None:
             snap0 = snapshot_state(eng)
-        run_steps(eng, nb, use_graph)
+        eng.run(nb, use_graph=use_graph)
         extra += nb
         torch.cuda.synchronize(dev)
     warm_s = time.perf_counter() - t_w
     if snap0 is not None:
-        restore_state(eng, snap0)
-        eng.batches_done -= extra  # the control block's batch / step went back with the state
-    epochs = max(1, -(-steps // nb)) if whole_epochs else steps / nb
-    k = int(round(epochs * nb))
+        restore_state(eng, snap0)  # the control block's batch / step go back with the state
+    k = max(1, steps)
+    epochs = k / nb
+    # rows of the k timed batches: the epoch's last batch is the short one
+    sizes = [min(global_batch, n_rows - b * global_batch) for b in range(nb)]
+
+    def rows_of(pos, n):  # rows of n consecutive batches from batch `pos` of an epoch
+        return (n // nb) * n_rows + sum(sizes[(pos + j) % nb] for j in range(n % nb))
+    rows_timed = rows_of(eng.batches_done % nb, k)
     _barrier(group, dev)
     torch.cuda.synchronize(dev)
     e0 = pipe.stats["epochs"]
@@ -644,16 +693,46 @@ def measure(cfg, ds, train, world, rank, dev, group, global_batch, steps, warmup
     # the trained state as the timed epochs left it: the quality figures are taken from
     # it, after the frozen run and the kernel timings below (restore_state)
     snap = snapshot_state(eng)
+    if dump_dir is not None:
+        # The last timed steps once more, from the seeded state (snap_seed), and what they
+        # hand their caller.  The trained state itself cannot be compared between runs: the
+        # scatter's float atomics sum in an order that varies, and Adam turns those
+        # roundings into 5e-3 of a weight's range within 8 steps wherever a gradient
+        # element is near zero, 1e-2 and more after a few hundred.  What does
+        # repeat: the parameters after DUMP_PARAM_STEPS steps (Adam with its moments and
+        # bias correction at work) and the loss of every one of DUMP_LOSS_STEPS steps, which
+        # follows the gradients and every Adam step so far.  The batches are those at the
+        # last timed steps' places in the epoch stream the engine holds (those steps' own
+        # batches, unless they ran into an epoch that is no longer in place).
+        r = min(DUMP_LOSS_STEPS, k, nb)
+        s = min(DUMP_PARAM_STEPS, r)
+        first = (eng.batches_done - r) % nb
+        restore_state(eng, snap_seed)
+        eng.ctl[0:1].fill_(first)
+        eng.run(s, use_graph=use_graph)
+        params = {name: p.detach().clone() for name, p in model.state_dict().items()}
+        if r > s:
+            eng.run(r - s, use_graph=use_graph)
+        torch.cuda.synchronize(dev)
+        # a collective with zero1: every rank
+        step_loss = eng.epoch_losses()[[(first + j) % nb for j in range(r)]]
+        if rank == 0:
+            params["loss"] = torch.from_numpy(step_loss)
+            dump_outputs(dump_dir, params)
+        del params
+        restore_state(eng, snap)
     # the same steps on the current epoch stream, reused (the step kernel wraps to the
     # epoch's first batch): the device + exchange rate beside `value`
-    _barrier(group, dev)
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    eng.run(k, use_graph=use_graph)
-    torch.cuda.synchronize(dev)
-    dtf = time.perf_counter() - t0
-    _barrier(group, dev)
-    dtf = _max_over_ranks(dtf, group, dev)
+    dtf = None
+    if full:
+        _barrier(group, dev)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        eng.run(k, use_graph=use_graph)
+        torch.cuda.synchronize(dev)
+        dtf = time.perf_counter() - t0
+        _barrier(group, dev)
+        dtf = _max_over_ranks(dtf, group, dev)
     ne = max(1, int(np.ceil(epochs)))
     hm = pipe.stats.get("host_ms", [])[-ne:]
     host = {k2: float(np.mean([h[k2] for h in hm if k2 in h])) for k2 in ("sample", "words", "stage")
@@ -671,7 +750,7 @@ def measure(cfg, ds, train, world, rank, dev, group, global_batch, steps, warmup
     # already built during the warm-up
     sustained = None
     ns = SUSTAINED_EPOCHS if nb <= EARLY_MAX_STEPS else min(1, SUSTAINED_EPOCHS)
-    if whole_epochs and ns > 0:
+    if full and whole_epochs and ns > 0:
         restore_state(eng, snap)
         _barrier(group, dev)
         torch.cuda.synchronize(dev)
@@ -689,17 +768,21 @@ def measure(cfg, ds, train, world, rank, dev, group, global_batch, steps, warmup
                      "host_stage_ms": float(np.mean([h["stage"] for h in hs if "stage" in h])) if hs else None,
                      "note": "consecutive fresh epochs after the timed ones, every epoch's host sampling and device "
                              "build (rows, permutation, grouping on a side stream) inside the region; `value` times "
-                             "the driver's epochs, whose streams the warm-up prefetched"}
+                             "the driver's epochs, whose streams the warm-up prefetched.  The region is `epochs` x "
+                             "steps_per_epoch steps from where the timed steps ended (mid-epoch unless --steps is a "
+                             "multiple of the epoch): any such run of steps holds exactly `epochs` x rows_per_epoch "
+                             "rows, and `fresh_epochs` counts the epoch boundaries it crossed"}
         ev = pipe.device_ms()
         if ev is not None:
             sustained["device_build_ms_per_epoch"] = float(ev[0] + ev[1])
-    return {"eng": eng, "model": model, "pipe": pipe, "snap": snap, "value": epochs * n_rows / dt, "dt": dt, "steps": k,
+    return {"eng": eng, "model": model, "pipe": pipe, "snap": snap, "value": rows_timed / dt, "dt": dt, "steps": k,
             "sustained": sustained,
             "epochs": epochs, "fresh_epochs": fresh, "rows_per_epoch": n_rows, "batches_per_epoch": nb,
             "warmup_run": {"steps": warm + extra, "seconds": round(warm_s, 3), "trained_steps_kept": warm,
                            "note": f"untimed: whole epochs, >= --warmup steps and >= {WARM_S} s (device ramp on a fresh box); "
                                    "the trained state of the steps past --warmup is discarded"},
-            "final_loss": final_loss, "frozen_value": k * n_rows / nb / dtf, "frozen_ms_per_step": dtf / k * 1e3,
+            "final_loss": final_loss, "frozen_value": rows_of(eng.batches_done % nb, k) / dtf if full else None,
+            "frozen_ms_per_step": dtf / k * 1e3 if full else None,
             "epoch_host_ms": host}
 
 
@@ -793,8 +876,15 @@ def layered_profile(config):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200, help="timed steps, rounded up to whole epochs")
+    ap.add_argument("--steps", type=int, default=200, help="timed steps")
     ap.add_argument("--warmup", type=int, default=20, help="warm-up steps, rounded up to whole epochs")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: frozen / sustained rates, per-kernel timings, rooflines, weak scaling "
+                         "(N > 1), HR@10 / NDCG@10, the Trainer.fit e2e figure and the CPU baseline (the options below "
+                         "that shape those apply with --full only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed steps, run once more from the seeded model, hand their caller "
+                         "(the parameters after two of them, the loss of each of up to 64) as DIR/<name>.npy")
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--kernel-steps", type=int, default=20, help="eager steps timed per kernel with HIP events")
@@ -853,8 +943,46 @@ def main():
     # ---- headline: the reference's global batch split over the N ranks (strong
     # scaling), whole fresh epochs
     m = measure(args.config, ds, train, world, rank, dev, group, global_batch, args.steps, args.warmup, use_graph,
-                whole_epochs=not args.profile_run)
+                whole_epochs=not args.profile_run, full=args.full, dump_dir=args.dump_outputs)
     eng, model, pipe = m["eng"], m["model"], m["pipe"]
+    dt, k = m["dt"], m["steps"]
+    head = {
+        "metric": METRIC,
+        "value": m["value"],
+        "unit": "interactions/s",
+        "n_gpus": world,
+        "steps": k,
+        "warmup": args.warmup,
+        "warmup_run": m["warmup_run"],
+        "ms_per_step": dt / k * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "data": (f"synthetic {shape}-shaped ({U - 1:,} users x {I - 1:,} items, {len(ds['train_users']):,} "
+                 f"train positives, 4 bit-exact sampled negatives each); {k} steps timed ({m['epochs']:.2f} epochs "
+                 f"of {m['batches_per_epoch']} steps), each epoch with fresh negatives and permutation "
+                 f"({m['fresh_epochs']} epoch boundaries in the timed region); seed 0"),
+        "config": {"workload": f"{args.config.upper()}: NCF(user_num={U}, item_num={I}, factor_num={f}, "
+                               f"num_layers={nl}, {mtype}), Adam lr 1e-3"
+                               + (f"; response distillation (T 2.0, alpha 0.5) from a random-init teacher "
+                                  f"NCF({C5_TEACHER[0]}, {C5_TEACHER[1]}, {C5_TEACHER[2]}) whose logits of "
+                                  f"each epoch stream are one forward launch at the epoch boundary"
+                                  if args.config == "c5" else ""),
+                   "global_batch": global_batch, "per_gpu_batch": per_gpu, "parallelism": f"dp{world}",
+                   "mlp_layers": [int(2 * f * 2 ** (nl - 1)) >> j for j in range(nl + 1)],
+                   "dp_exchange": eng.dp_mode, "hip_graph": use_graph,
+                   "rows_per_epoch": m["rows_per_epoch"], "steps_per_epoch": m["batches_per_epoch"]},
+        "setup_s": {"data": round(t_data, 2)},
+    }
+    if not args.full:  # a plain run: the headline only
+        pipe.close()
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            _barrier(group, dev)
+            torch.distributed.destroy_process_group()
+        return head if rank == 0 else None
 
     # ---- per-kernel live timing (HIP events on the launch stream) -------------
     kt = eng.time_kernels(args.kernel_steps)
@@ -952,34 +1080,8 @@ def main():
         cpu = None
         if not args.skip_cpu_baseline and world == 1:
             cpu = cpu_baseline_child(args.config, args.cpu_seconds, not args.no_script_epoch)
-        dt, k = m["dt"], m["steps"]
         out = {
-            "metric": METRIC,
-            "value": m["value"],
-            "unit": "interactions/s",
-            "n_gpus": world,
-            "steps": k,
-            "warmup": args.warmup,
-            "warmup_run": m["warmup_run"],
-            "ms_per_step": dt / k * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "fp32",
-            "data": (f"synthetic {shape}-shaped ({U - 1:,} users x {I - 1:,} items, {len(ds['train_users']):,} "
-                     f"train positives, 4 bit-exact sampled negatives each); {m['epochs']} whole epochs timed "
-                     f"({k} steps, requested {args.steps}, rounded up), each with fresh negatives and permutation "
-                     f"({m['fresh_epochs']} epoch boundaries in the timed region); seed 0"),
-            "config": {"workload": f"{args.config.upper()}: NCF(user_num={U}, item_num={I}, factor_num={f}, "
-                                   f"num_layers={nl}, {mtype}), Adam lr 1e-3"
-                                   + (f"; response distillation (T 2.0, alpha 0.5) from a random-init teacher "
-                                      f"NCF({C5_TEACHER[0]}, {C5_TEACHER[1]}, {C5_TEACHER[2]}) whose logits of "
-                                      f"each epoch stream are one forward launch at the epoch boundary"
-                                      if args.config == "c5" else ""),
-                       "global_batch": global_batch, "per_gpu_batch": per_gpu, "parallelism": f"dp{world}",
-                       "mlp_layers": [int(2 * f * 2 ** (nl - 1)) >> j for j in range(nl + 1)],
-                       "dp_exchange": eng.dp_mode, "hip_graph": use_graph,
-                       "rows_per_epoch": m["rows_per_epoch"], "steps_per_epoch": m["batches_per_epoch"]},
+            **head,
             "roofline": {"bound": "mfma", "achieved": executed_tf, "peak": 157.3, "unit": "TFLOP/s",
                          "frac": executed_tf / 157.3, "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": kname, "kernel_ms": ms, "flops_per_launch": xflops,
@@ -1008,7 +1110,6 @@ def main():
                                      "permutation): device + exchange rate"},
             "weak_scaling": weak,
             "cpu_baseline": cpu,
-            "setup_s": {"data": round(t_data, 2)},
         }
         if path != L.PATH_FUSED and f % 4 == 0:
             # the layered GEMMs run on v_mfma_f32_16x16x32_bf16 (six bf16 products per fp32

@@ -43,10 +43,10 @@ if has tests; then
     run pytest_gpu 1100 python -u -m pytest ${TESTS:-tests -m gpu} -v -s -x --timeout 500 --timeout-method thread \
         -p no:cacheprovider
 fi
-has bench && run bench 600 python bench.py
+has bench && run bench 600 python bench.py --full
 if has configs; then
     for cfg in ${CONFIGS:-c2 c4 cli stress c5}; do
-        run "bench_$cfg" 300 python bench.py --config "$cfg" --steps 200 --warmup 20 --skip-cpu-baseline \
+        run "bench_$cfg" 300 python bench.py --full --config "$cfg" --steps 200 --warmup 20 --skip-cpu-baseline \
             --e2e-epochs "${E2E:-2}"
         tail -1 "gpurun_out/bench_$cfg.log" >> gpurun_out/configs.jsonl
     done
@@ -71,10 +71,10 @@ if has profile; then
 fi
 if has multirank; then
     export NCF_BENCH_SAME_DEVICE=1 NCF_BENCH_BACKEND=gloo
-    run mr_spawn2_c3 300 python bench.py --gpus 2 --steps 20 --warmup 5
+    run mr_spawn2_c3 300 python bench.py --full --gpus 2 --steps 20 --warmup 5
     run mr_run2_c3 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5
-    run mr_spawn3_c4 400 env NCF_BENCH_SUSTAINED_EPOCHS=0 python bench.py --gpus 3 --config c4 --no-weak \
+        --master-port 29533 bench.py --full --gpus 2 --steps 20 --warmup 5
+    run mr_spawn3_c4 400 env NCF_BENCH_SUSTAINED_EPOCHS=0 python bench.py --full --gpus 3 --config c4 --no-weak \
         --skip-eval --steps 20 --warmup 5
     unset NCF_BENCH_SAME_DEVICE NCF_BENCH_BACKEND
 fi

@@ -6,7 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-ARGS="--config ${CONFIG:-c3} --steps 30 --warmup 5 --skip-cpu-baseline --skip-eval --kernel-steps 3 --e2e-epochs 0"
+ARGS="--full --config ${CONFIG:-c3} --steps 30 --warmup 5 --skip-cpu-baseline --skip-eval --kernel-steps 3 --e2e-epochs 0"
 export FILTER="${FILTER:-ncf_step_kernel reduce_adam}"
 P1="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVES"
 P2="SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_WAIT_INST_LDS"

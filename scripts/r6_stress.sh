@@ -23,13 +23,13 @@ fi
 if has bench; then
   for v in $AB_VALS; do
     val=$v; [ "$v" = default ] && val=
-    env $AB_VAR=$val timeout -k 10 200 python bench.py --config ${CFG:-stress} --steps 50 --warmup 10 --skip-cpu-baseline \
+    env $AB_VAR=$val timeout -k 10 200 python bench.py --full --config ${CFG:-stress} --steps 50 --warmup 10 --skip-cpu-baseline \
       --no-script-epoch --e2e-epochs 0 > $O/bench_${AB_VAR}_$v.log 2>&1 || { tail -20 $O/bench_${AB_VAR}_$v.log; exit 1; }
     python3 -c "import json;l=[x for x in open('$O/bench_${AB_VAR}_$v.log') if x.startswith('{')][-1];d=json.loads(l);print('$AB_VAR=$v',round(d['value']/1e6,2),'M/s',round(d['ms_per_step']*1e3,1),'us/step', 'sustained', round(d['sustained']['value']/1e6,2) if d.get('sustained') else None)"
   done
 fi
 if has prof; then
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof${PTAG:-} -o run -- python3 bench.py --config ${CFG:-stress} --steps 20 --warmup 4 \
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof${PTAG:-} -o run -- python3 bench.py --full --config ${CFG:-stress} --steps 20 --warmup 4 \
      --skip-cpu-baseline --no-script-epoch --e2e-epochs 0 --skip-eval > $O/prof.log 2>&1 || { tail -20 $O/prof.log; exit 1; }
   f=$(find $O/prof${PTAG:-} -name "*kernel_stats.csv" | head -1)
   python3 -c "

@@ -20,7 +20,7 @@ if has bench; then
   done
 fi
 if has prof; then
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o stress -- python3 bench.py --config stress --steps 20 --warmup 4 \
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o stress -- python3 bench.py --full --config stress --steps 20 --warmup 4 \
      --skip-cpu-baseline --no-script-epoch --e2e-epochs 0 --skip-eval > $O/prof.log 2>&1 || { tail -20 $O/prof.log; exit 1; }
   f=$(find $O/prof -name "*kernel_stats.csv" | head -1); head -16 "$f" | cut -c1-160
 fi

@@ -59,6 +59,29 @@ def test_failed_rank_stops_the_others():
     assert r.returncode != 0 and not [x for x in r.stdout.splitlines() if x.startswith("{")]
 
 
+def test_dump_outputs_writes_float32_and_keeps_to_its_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per array in its own shape; above the budget the
+    larger arrays become the same seeded sample on every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {"a.weight": torch.randn(300, 40, generator=g), "loss": torch.randn(7, generator=g).double()}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    a = np.load(tmp_path / "all" / "a.weight.npy")
+    assert a.dtype == np.float32 and a.shape == (300, 40) and np.array_equal(a, arrays["a.weight"].numpy())
+    loss = np.load(tmp_path / "all" / "loss.npy")
+    assert loss.dtype == np.float32 and np.array_equal(loss, arrays["loss"].float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 16384)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    s1, s2 = np.load(tmp_path / "s1" / "a.weight.npy"), np.load(tmp_path / "s2" / "a.weight.npy")
+    assert s1.dtype == np.float32 and s1.ndim == 1 and 0 < s1.size < 12000 and np.array_equal(s1, s2)
+    assert np.isin(s1, a).all() and np.load(tmp_path / "s1" / "loss.npy").shape == (7,)
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= 16384
+
+
 def test_roofline_traffic_sources_in_committed_profiles():
     """Every bench config's roofline finds its counter traffic in a committed
     rocprofv3 summary: the fused path by its launch group's kernel names, the layered

@@ -21,7 +21,9 @@
 extern "C" {
 #endif
 
-/* 19: NCF_LAYOUT_FACT_IN_ADAM (0x20) removed -- measured slower than the two launches it
+/* 20: full-catalogue top-K inference: ncf_recommend_workspace_bytes, ncf_recommend,
+ * ncf_debug_set_recommend_path.
+ * 19: NCF_LAYOUT_FACT_IN_ADAM (0x20) removed -- measured slower than the two launches it
  * replaced; the bit is retired (NCF_LAYOUT_RETIRED_0X20: rejected by
  * ncf_reduce_adam_step).
  * 18: in-step Adam for small batches: ncf_ais_bufs, ncf_ais_supported, ncf_ais_begin,
@@ -35,7 +37,7 @@ extern "C" {
  * 15: ncf_layout.flags gains the fused step's workgroup geometry (NCF_LAYOUT_GEO_*) and
  * NCF_LAYOUT_FACT_DEFER_DX; new ncf_adam_step_fact, ncf_prepare_epoch2
  * (NCF_PREP_CANONICAL), ncf_probe_gather_scatter, ncf_debug_set_geometry. */
-#define NCF_ABI_VERSION 19
+#define NCF_ABI_VERSION 20
 
 #define NCF_OK 0
 #define NCF_E_UNSUPPORTED (-1) /* (model_type, factor_num, num_layers) has no compiled kernel */
@@ -596,6 +598,46 @@ int ncf_build_rows(const int32_t *pos_users, const int32_t *pos_items, int64_t n
  */
 int ncf_hr_ndcg(const float *logits, const int32_t *items, int64_t n, int batch, int top_k,
                 int32_t *hr, float *ndcg, void *stream);
+
+/*
+ * Full-catalogue top-K recommendation (since ABI 20).  The reference only ranks a test
+ * user's held-out item against 99 sampled negatives (src/training/metrics.py:4-25); this
+ * gives every queried user their best top_k items of the whole catalogue.
+ *
+ * users[q], q < n_users: queried user ids (duplicates allowed; the caller range-checks
+ * them, as for ncf_forward).  items_out[q * top_k + r] / scores_out[...]: the r-th best
+ * item of users[q] and its logit (NCF.forward(u, i) in eval mode, models.py:97-118;
+ * dropout is never applied).  Order: score descending, then item id ascending -- a
+ * function of the scores alone, whatever the tiling or the split of the item range.
+ * seen_ptr (user_num + 1 entries, indexed by user id) / seen_items: CSR of items left
+ * out, ascending and unique inside a user; both NULL = no exclusion.  A user with fewer
+ * than top_k eligible items gets item -1 and score -inf in the trailing slots.
+ * 1 <= top_k <= 128, else NCF_E_ARG; n_users == 0 returns NCF_OK.
+ *
+ * Two paths, chosen from the layout (every shape ncf_supported accepts):
+ *   NCF_PATH_FUSED shapes: a prologue projects the catalogue and the queried users
+ *     through layer 0 (Pi = Im W0[:, dm:]^T + b0, Pu = Um W0[:, :dm]^T, Ag = wp * Ug) and
+ *     one kernel scores user tiles against LDS-staged item chunks on MFMA tiles and
+ *     keeps a running top-K per user; the item range is split over workgroups and a
+ *     merge pass orders the partial lists.  Workspace: the projections
+ *     ((item_num + n_users) * max(16, dm) + n_users * max(16, f) floats) and
+ *     n_users * splits * top_k (score, item) pairs.
+ *   other shapes: in user chunks of at most 131,072 (user, item) pairs (at least one
+ *     user), the packed rows are written, ncf_forward scores them and a select kernel
+ *     applies the same mask, order and list.  Workspace: 12 bytes per pair of one chunk
+ *     plus ncf_forward_workspace_bytes of that many rows.
+ * ncf_recommend_workspace_bytes: bytes of `workspace` for such a call (-1: bad argument).
+ */
+int64_t ncf_recommend_workspace_bytes(const ncf_layout *lay, int64_t n_users, int top_k);
+int ncf_recommend(const ncf_layout *lay, const float *params,
+                  const int32_t *users, int64_t n_users, int top_k,
+                  const int64_t *seen_ptr, const int32_t *seen_items,
+                  int32_t *items_out, float *scores_out,
+                  void *workspace, int64_t workspace_bytes, void *stream);
+/* Tests only: NCF_PATH_LAYERED sends later ncf_recommend calls (and their workspace
+ * sizes) through the materialised path whatever the shape; 0 restores the choice from
+ * the layout.  NCF_E_ARG otherwise. */
+int ncf_debug_set_recommend_path(int path);
 
 /* Diagnostics only: ablation switches for the next ncf_train_step launches
  * (1 = skip embedding scatter-add, 2 = skip weight-gradient MFMAs).  Results are

@@ -29,7 +29,7 @@ NCF_E_ARG = -2
 NCF_E_LAUNCH = -3
 MODEL_GMF, MODEL_MLP, MODEL_NEUMF = 0, 1, 2
 DZ_BCE, DZ_DLOGIT, DZ_KD = 0, 1, 2
-ABI_VERSION = 19  # include/ncf_hip.h NCF_ABI_VERSION
+ABI_VERSION = 20  # include/ncf_hip.h NCF_ABI_VERSION
 PATH_FUSED, PATH_LAYERED = 1, 2  # ncf_supported()
 LAYOUT_PER_ROW_L0, LAYOUT_WG_SHIFT, LAYOUT_WG_MASK = 0x1, 8, 0xFFF  # ncf_layout.flags (ncf_layout_tune)
 LAYOUT_LAYERED = 0x2  # ncf_layout.flags: training on the layered path even where a fused kernel exists
@@ -127,6 +127,10 @@ _HIP_PROTOS = {
     "ncf_prepare_epoch": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, ctypes.c_int, c_vp, c_vp, c_i64, c_vp]),
     "ncf_prepare_epoch2": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_i64,
                                           c_vp]),
+    "ncf_recommend_workspace_bytes": (c_i64, [ctypes.POINTER(NcfLayout), c_i64, ctypes.c_int]),
+    "ncf_recommend": (ctypes.c_int, [ctypes.POINTER(NcfLayout), c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp, c_i64, c_vp]),
+    "ncf_debug_set_recommend_path": (ctypes.c_int, [ctypes.c_int]),
     "ncf_hr_ndcg": (ctypes.c_int, [c_vp, c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "ncf_fact_mode": (ctypes.c_int, [c_vp]),
     "ncf_reduce_rows": (ctypes.c_int, [c_vp]),

@@ -1,0 +1,673 @@
+// Full-catalogue top-K recommendation (ncf_recommend, include/ncf_hip.h; since ABI 20).
+//
+// Fused path (every shape with a fused kernel: dm <= 64).  Layer 0 factors per entity,
+//   pre0(u, i) = Pu[u] + Pi[i],  Pu = Um W0[:, :dm]^T,  Pi = Im W0[:, dm:]^T + b0,
+// so a prologue projects the catalogue and the queried users once and the main kernel
+// does, per pair, one add + ReLU of width dm, layers 1..L-1 on v_mfma_f32_16x16x4_f32,
+// the predict dot and the GMF dot (user side pre-scaled by the predict weights).  No
+// per-pair gathers and no U x I array.
+//
+// Register layout of a 16-item tile of one user (one wave): lane l = (g = l >> 4,
+// it = l & 15) holds, for item `it`, the activations of columns 16 t + 4 g + r
+// (t = 16-column tile, r = 0..3) as f4 h[t].  That is the B operand of MFMA4 for K-step
+// (t, r) (B[k = g][j = it]); the A operand is W[16 o + it][16 t + 4 g + r], one 16-byte
+// LDS read per four MFMAs, and the result D[i = 4 g + r'][j = it] is output column
+// 16 o + 4 g + r' of item `it` -- the same layout again, so the tower runs in registers
+// with no transposes.  Widths below 16 are zero padded (weights, biases, Pi, Pu).
+//
+// A workgroup (4 waves) owns a tile of 4 or 16 queried users and a range of 64-item
+// chunks; each chunk (Pi rows, Ig rows) is staged once in LDS and shared by the tile's
+// users.  Each (wave, user) keeps a sorted top-K list in LDS (score descending, item id
+// ascending) with a threshold test against its last entry.  The item range is split
+// over workgroups (grid.y); a merge pass orders the partial lists.  The order is total
+// on (score, id) and every score is one fixed arithmetic sequence, so the result does
+// not depend on tiling, the split or the users per workgroup.
+//
+// Materialised path (the other accepted shapes): user chunks of at most RC_MAT_PAIRS
+// (user, item) pairs -- rows kernel, ncf_forward, select-from-logits with the same
+// mask, order and list.
+#include <string.h>
+
+#include "ncf_common.h"
+
+namespace ncf {
+
+constexpr int RC_WAVES = 4;
+constexpr int RC_CH = 64;  // items per LDS chunk (one seen-mask bit per lane)
+constexpr int RC_MAXK = 128;
+constexpr int RC_IDMAX = 0x7fffffff;      // id of an empty list slot (sorts last)
+constexpr int64_t RC_MAT_PAIRS = 1 << 17;  // materialised path: (user, item) pairs per chunk
+constexpr int RC_LDS_LIMIT = 160 * 1024;
+
+static int g_rc_path = 0;  // ncf_debug_set_recommend_path
+
+__host__ __device__ constexpr int rc_max(int a, int b) { return a > b ? a : b; }
+
+template <int F_, int L_, int MODE_>
+struct RcShape {
+    static constexpr int F = F_, MODE = MODE_;
+    static constexpr bool GMF = MODE != NCF_MODEL_MLP;
+    static constexpr bool MLP = MODE != NCF_MODEL_GMF;
+    static constexpr int L = MLP ? L_ : 1;
+    static constexpr int DM = F << (L - 1);
+    static constexpr int NL = MLP ? L - 1 : 0;  // tower layers after layer 0
+    // padded width of layer k's output (k = 0: the layer-0 activation h1)
+    __host__ __device__ static constexpr int KP(int k) { return rc_max(16, DM >> k); }
+    __host__ __device__ static constexpr int T(int k) { return KP(k) / 16; }
+    __host__ __device__ static constexpr int SW(int k) { return KP(k - 1) + 4; }  // LDS row stride of W_k
+    __host__ __device__ static constexpr int wsize(int k) { return (MLP && k >= 1 && k <= NL) ? KP(k) * SW(k) : 0; }
+    __host__ __device__ static constexpr int woff(int k) { return k <= 1 ? 0 : woff(k - 1) + wsize(k - 1); }
+    __host__ __device__ static constexpr int boff(int k) { return k <= 1 ? 0 : boff(k - 1) + KP(k - 1); }
+    static constexpr int W_TOTAL = woff(NL + 1);
+    static constexpr int B_TOTAL = MLP ? boff(NL + 1) : 0;
+    static constexpr int WP = MLP ? KP(NL) : 0;  // padded predict weights of the tower output
+    static constexpr int KP0 = MLP ? KP(0) : 0;
+    static constexpr int SP = MLP ? KP0 + 4 : 0;  // LDS row stride of the staged Pi chunk
+    static constexpr int FP = GMF ? rc_max(16, F) : 0;
+    static constexpr int TG = FP / 16;
+    static constexpr int SG = GMF ? FP + 4 : 0;   // LDS row stride of the staged Ig chunk
+    static constexpr int POFF = MODE == NCF_MODEL_NEUMF ? F : 0;
+    static constexpr int FIXED = W_TOTAL + B_TOTAL + WP + RC_CH * (SP + SG);  // floats, all % 4 == 0
+};
+
+struct RcArgs {
+    ncf_layout lay;
+    const float* params;
+    const int32_t* users;
+    int64_t nq;
+    int K;
+    const int64_t* seen_ptr;
+    const int32_t* seen_items;
+    const float* Pi;  // [I][KP0]
+    const float* Pu;  // [nq][KP0]
+    const float* Ag;  // [nq][FP]
+    float* part_s;    // [nq][nsplit][K]
+    int32_t* part_i;
+    int nsplit, cps;  // item splits; chunks per split
+    int upw;          // users per wave
+};
+
+__device__ __forceinline__ bool rc_better(float s, int id, float ts, int ti) {
+    return s > ts || (s == ts && id < ti);
+}
+
+// Wave-wide insert of the candidates lanes 0..15 hold (ascending ids) into the sorted
+// list ls / li of K entries.  The common case is the one compare against entry K - 1.
+__device__ __forceinline__ void rc_feed(volatile float* ls, volatile int* li, int K, float s, int id, bool valid,
+                                        int lane) {
+    float ts = ls[K - 1];
+    int ti = li[K - 1];
+    unsigned long long m = __ballot(valid && rc_better(s, id, ts, ti));
+    while (m) {
+        const int src = __ffsll((long long)m) - 1;
+        const float cs = __shfl(s, src, 64);
+        const int ci = __shfl(id, src, 64);
+        const int j0 = lane, j1 = lane + 64;
+        float e0s = 0.f, e1s = 0.f;
+        int e0i = 0, e1i = 0;
+        if (j0 < K) { e0s = ls[j0]; e0i = li[j0]; }
+        if (j1 < K) { e1s = ls[j1]; e1i = li[j1]; }
+        const bool b0 = j0 < K && rc_better(e0s, e0i, cs, ci);
+        const bool b1 = j1 < K && rc_better(e1s, e1i, cs, ci);
+        const int pos = __popcll(__ballot(b0)) + __popcll(__ballot(b1));  // entries ahead of the candidate
+        if (j0 < K && !b0 && j0 + 1 < K) { ls[j0 + 1] = e0s; li[j0 + 1] = e0i; }
+        if (j1 < K && !b1 && j1 + 1 < K) { ls[j1 + 1] = e1s; li[j1 + 1] = e1i; }
+        if (lane == 0) { ls[pos] = cs; li[pos] = ci; }
+        ts = ls[K - 1];
+        ti = li[K - 1];
+        m &= m - 1;
+        m &= __ballot(valid && rc_better(s, id, ts, ti));
+    }
+}
+
+__device__ __forceinline__ void rc_list_init(volatile float* ls, volatile int* li, int K, int lane) {
+    for (int j = lane; j < K; j += 64) {
+        ls[j] = -INFINITY;
+        li[j] = RC_IDMAX;
+    }
+}
+
+// First position p in [lo, hi) with seen_items[p] >= item (wave-uniform).
+__device__ __forceinline__ int64_t rc_lower_bound(const int32_t* __restrict__ seen_items, int64_t lo, int64_t hi,
+                                                  int item) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (seen_items[mid] < item) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// Seen mask of the 64 items [c0, c0 + 64) of a user whose cursor *cur points at the first
+// list entry >= c0: bit j = item c0 + j is in the list.  The list is ascending and unique,
+// so at most 64 entries fall in the chunk and one load per lane covers them; every access
+// is bounded by hi = seen_ptr[u + 1].  scr: 64 ints of per-wave LDS.
+__device__ __forceinline__ unsigned long long rc_seen_mask(const int32_t* __restrict__ seen_items, int64_t* cur,
+                                                           int64_t hi, int c0, volatile int* scr, int lane) {
+    const int64_t p = *cur + lane;
+    const int v = p < hi ? seen_items[p] : RC_IDMAX;
+    const bool below = p < hi && v < c0 + RC_CH;
+    scr[lane] = 0;
+    if (below && v >= c0) scr[v - c0] = 1;
+    const unsigned long long mask = __ballot(scr[lane] != 0);
+    *cur += __popcll(__ballot(below));
+    return mask;
+}
+
+template <int TIN, int TOUT>
+__device__ __forceinline__ void rc_layer(const f4 (&in)[TIN], f4 (&out)[TOUT], const float* W, const float* bias,
+                                         int it, int g) {
+    constexpr int SW = 16 * TIN + 4;
+#pragma unroll
+    for (int o = 0; o < TOUT; ++o) {
+        f4 acc = *reinterpret_cast<const f4*>(bias + 16 * o + 4 * g);
+#pragma unroll
+        for (int t = 0; t < TIN; ++t) {
+            const f4 w = *reinterpret_cast<const f4*>(W + (16 * o + it) * SW + 16 * t + 4 * g);
+            acc = MFMA4(w.x, in[t].x, acc);
+            acc = MFMA4(w.y, in[t].y, acc);
+            acc = MFMA4(w.z, in[t].z, acc);
+            acc = MFMA4(w.w, in[t].w, acc);
+        }
+        out[o].x = fmaxf(acc.x, 0.f);
+        out[o].y = fmaxf(acc.y, 0.f);
+        out[o].z = fmaxf(acc.z, 0.f);
+        out[o].w = fmaxf(acc.w, 0.f);
+    }
+}
+
+template <int TN>
+__device__ __forceinline__ float rc_dot(const f4 (&h)[TN], const float* w, int g) {
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < TN; ++t) {
+        const f4 v = *reinterpret_cast<const f4*>(w + 16 * t + 4 * g);
+        s = fmaf(h[t].x, v.x, s);
+        s = fmaf(h[t].y, v.y, s);
+        s = fmaf(h[t].z, v.z, s);
+        s = fmaf(h[t].w, v.w, s);
+    }
+    return s;
+}
+
+// Prologue: Pi (b0 folded in), Pu and Ag = wp[:F] * Ug[u], zero padded to KP0 / FP columns.
+__global__ __launch_bounds__(256) void rc_proj_kernel(ncf_layout lay, const float* __restrict__ prm,
+                                                      const int32_t* __restrict__ users, int64_t nq, int KP0, int FP,
+                                                      float* __restrict__ Pi, float* __restrict__ Pu,
+                                                      float* __restrict__ Ag) {
+    const int DM = lay.factor_num << (lay.num_layers - 1);
+    const int F = lay.factor_num;
+    const int64_t n_pi = (int64_t)lay.item_num * KP0, n_pu = nq * KP0, n_ag = nq * FP;
+    int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx < n_pi + n_pu) {
+        const bool item = idx < n_pi;
+        if (!item) idx -= n_pi;
+        const int64_t row = idx / KP0;
+        const int c = (int)(idx - row * KP0);
+        float acc = 0.f;
+        if (c < DM) {
+            const float* w = prm + lay.w[0] + (int64_t)c * 2 * DM + (item ? DM : 0);
+            const float* x = item ? prm + lay.im + row * DM : prm + lay.um + (int64_t)users[row] * DM;
+            for (int k = 0; k < DM; ++k) acc = fmaf(x[k], w[k], acc);
+            if (item) acc += prm[lay.b[0] + c];
+        }
+        (item ? Pi : Pu)[idx] = acc;
+        return;
+    }
+    idx -= n_pi + n_pu;
+    if (idx < n_ag) {
+        const int64_t q = idx / FP;
+        const int f = (int)(idx - q * FP);
+        Ag[idx] = f < F ? prm[lay.wp + f] * prm[lay.ug + (int64_t)users[q] * F + f] : 0.f;
+    }
+}
+
+template <int F, int L, int MODE>
+__global__ __launch_bounds__(RC_WAVES * 64) void rc_kernel(RcArgs a) {
+    using C = RcShape<F, L, MODE>;
+    extern __shared__ f4 rc_smem4[];
+    float* const smem = reinterpret_cast<float*>(rc_smem4);
+    float* const Wl = smem;
+    float* const Bl = Wl + C::W_TOTAL;
+    float* const WPl = Bl + C::B_TOTAL;
+    float* const PiL = WPl + C::WP;
+    float* const IgL = PiL + RC_CH * C::SP;
+    const int K = a.K, UT = RC_WAVES * a.upw;
+    float* const lists_s = IgL + RC_CH * C::SG;
+    int* const lists_i = reinterpret_cast<int*>(lists_s + UT * K);
+    int* const scr = lists_i + UT * K;                                       // [RC_WAVES][64]
+    int64_t* const cur = reinterpret_cast<int64_t*>(scr + RC_WAVES * 64);    // [UT] (8-byte aligned: see rc_lds_bytes)
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, it = lane & 15;
+    const float* __restrict__ prm = a.params;
+    const int I = a.lay.item_num;
+    const int nchunks = (I + RC_CH - 1) / RC_CH;
+    const int split = blockIdx.y;
+    const int cb = split * a.cps, ce = min(cb + a.cps, nchunks);
+    const int64_t q0 = (int64_t)blockIdx.x * UT;
+
+    // tower weights (zero padded), biases, predict weights
+    if constexpr (C::MLP) {
+#pragma unroll
+        for (int k = 1; k <= C::NL; ++k) {
+            const int rows = C::KP(k), cols = C::KP(k - 1), sw = C::SW(k);
+            const int out = C::DM >> k, in = C::DM >> (k - 1);
+            const float* w = prm + a.lay.w[k];
+            for (int idx = tid; idx < rows * cols; idx += RC_WAVES * 64) {
+                const int r = idx / cols, c = idx - r * cols;
+                Wl[C::woff(k) + r * sw + c] = (r < out && c < in) ? w[r * in + c] : 0.f;
+            }
+            for (int idx = tid; idx < rows; idx += RC_WAVES * 64)
+                Bl[C::boff(k) + idx] = idx < out ? prm[a.lay.b[k] + idx] : 0.f;
+        }
+        for (int idx = tid; idx < C::WP; idx += RC_WAVES * 64)
+            WPl[idx] = idx < F ? prm[a.lay.wp + C::POFF + idx] : 0.f;
+    }
+    const float bp = prm[a.lay.bp];
+
+    for (int uu = 0; uu < a.upw; ++uu) {
+        const int slot = wave * a.upw + uu;
+        rc_list_init(lists_s + slot * K, lists_i + slot * K, K, lane);
+        const int64_t q = q0 + slot;
+        if (a.seen_ptr != nullptr && q < a.nq && lane == 0) {
+            const int u = a.users[q];
+            cur[slot] = rc_lower_bound(a.seen_items, a.seen_ptr[u], a.seen_ptr[u + 1], cb * RC_CH);
+        }
+    }
+
+    for (int ch = cb; ch < ce; ++ch) {
+        const int c0 = ch * RC_CH;
+        __syncthreads();  // the previous chunk is consumed (first pass: weights and lists are written)
+        if constexpr (C::MLP) {
+            constexpr int C4 = C::KP0 / 4;
+            for (int idx = tid; idx < RC_CH * C4; idx += RC_WAVES * 64) {
+                const int r = idx / C4, c4 = idx - r * C4;
+                f4 v = {0.f, 0.f, 0.f, 0.f};
+                if (c0 + r < I) v = reinterpret_cast<const f4*>(a.Pi)[(int64_t)(c0 + r) * C4 + c4];
+                *reinterpret_cast<f4*>(PiL + r * C::SP + 4 * c4) = v;
+            }
+        }
+        if constexpr (C::GMF) {
+            for (int idx = tid; idx < RC_CH * C::FP; idx += RC_WAVES * 64) {
+                const int r = idx / C::FP, f = idx - r * C::FP;
+                IgL[r * C::SG + f] = (c0 + r < I && f < F) ? prm[a.lay.ig + (int64_t)(c0 + r) * F + f] : 0.f;
+            }
+        }
+        __syncthreads();
+
+        for (int uu = 0; uu < a.upw; ++uu) {
+            const int slot = wave * a.upw + uu;
+            const int64_t q = q0 + slot;
+            if (q >= a.nq) break;  // wave-uniform
+            unsigned long long seen = 0;
+            if (a.seen_ptr != nullptr) {
+                const int u = a.users[q];
+                int64_t c = cur[slot];
+                seen = rc_seen_mask(a.seen_items, &c, a.seen_ptr[u + 1], c0, scr + wave * 64, lane);
+                if (lane == 0) cur[slot] = c;
+            }
+            f4 pu[C::MLP ? C::T(0) : 1], ag[C::GMF ? C::TG : 1];
+            if constexpr (C::MLP) {
+#pragma unroll
+                for (int t = 0; t < C::T(0); ++t)
+                    pu[t] = reinterpret_cast<const f4*>(a.Pu)[q * (C::KP0 / 4) + 4 * t + g];
+            }
+            if constexpr (C::GMF) {
+#pragma unroll
+                for (int t = 0; t < C::TG; ++t)
+                    ag[t] = reinterpret_cast<const f4*>(a.Ag)[q * (C::FP / 4) + 4 * t + g];
+            }
+            volatile float* ls = lists_s + slot * K;
+            volatile int* li = lists_i + slot * K;
+#pragma unroll 1
+            for (int tt = 0; tt < RC_CH / 16; ++tt) {
+                if (c0 + 16 * tt >= I) break;
+                const int row = 16 * tt + it;
+                float part = 0.f;
+                if constexpr (C::MLP) {
+                    f4 h0[C::T(0)];
+#pragma unroll
+                    for (int t = 0; t < C::T(0); ++t) {
+                        const f4 p = *reinterpret_cast<const f4*>(PiL + row * C::SP + 16 * t + 4 * g);
+                        h0[t].x = fmaxf(pu[t].x + p.x, 0.f);
+                        h0[t].y = fmaxf(pu[t].y + p.y, 0.f);
+                        h0[t].z = fmaxf(pu[t].z + p.z, 0.f);
+                        h0[t].w = fmaxf(pu[t].w + p.w, 0.f);
+                    }
+                    if constexpr (C::NL == 0) {
+                        part = rc_dot(h0, WPl, g);
+                    } else {
+                        f4 h1[C::T(1)];
+                        rc_layer(h0, h1, Wl + C::woff(1), Bl + C::boff(1), it, g);
+                        if constexpr (C::NL == 1) {
+                            part = rc_dot(h1, WPl, g);
+                        } else {
+                            f4 h2[C::T(2)];
+                            rc_layer(h1, h2, Wl + C::woff(2), Bl + C::boff(2), it, g);
+                            if constexpr (C::NL == 2) {
+                                part = rc_dot(h2, WPl, g);
+                            } else {
+                                f4 h3[C::T(3)];
+                                rc_layer(h2, h3, Wl + C::woff(3), Bl + C::boff(3), it, g);
+                                part = rc_dot(h3, WPl, g);
+                            }
+                        }
+                    }
+                }
+                if constexpr (C::GMF) part += rc_dot(ag, IgL + row * C::SG, g);
+                part += shfl_xor(part, 16);
+                part += shfl_xor(part, 32);
+                const float z = part + bp;
+                const int item = c0 + row;
+                const bool valid = lane < 16 && item < I && !((seen >> row) & 1ull);
+                rc_feed(ls, li, K, z, item, valid, lane);
+            }
+        }
+    }
+
+    for (int uu = 0; uu < a.upw; ++uu) {
+        const int slot = wave * a.upw + uu;
+        const int64_t q = q0 + slot;
+        if (q >= a.nq) break;
+        const int64_t o = (q * a.nsplit + split) * K;
+        volatile float* ls = lists_s + slot * K;
+        volatile int* li = lists_i + slot * K;
+        for (int j = lane; j < K; j += 64) {
+            a.part_s[o + j] = ls[j];
+            a.part_i[o + j] = li[j];
+        }
+    }
+}
+
+// One wave per user: the nsplit sorted partial lists into the final K (empty slots:
+// item -1, score -inf).
+__global__ __launch_bounds__(RC_WAVES * 64) void rc_merge_kernel(const float* __restrict__ part_s,
+                                                                 const int32_t* __restrict__ part_i, int64_t nq,
+                                                                 int nsplit, int K, int32_t* __restrict__ items_out,
+                                                                 float* __restrict__ scores_out) {
+    extern __shared__ f4 rc_smem4[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    float* const lsf = reinterpret_cast<float*>(rc_smem4) + wave * 2 * K;
+    int* const lif = reinterpret_cast<int*>(lsf + K);
+    const int64_t q = (int64_t)blockIdx.x * RC_WAVES + wave;
+    if (q >= nq) return;
+    volatile float* ls = lsf;
+    volatile int* li = lif;
+    rc_list_init(ls, li, K, lane);
+    for (int s = 0; s < nsplit; ++s) {
+        const int64_t o = (q * nsplit + s) * K;
+        for (int j0 = 0; j0 < K; j0 += 16) {
+            const int j = j0 + lane;
+            float sc = 0.f;
+            int id = RC_IDMAX;
+            if (lane < 16 && j < K) { sc = part_s[o + j]; id = part_i[o + j]; }
+            rc_feed(ls, li, K, sc, id, id != RC_IDMAX, lane);
+        }
+    }
+    for (int j = lane; j < K; j += 64) {
+        const int id = li[j];
+        items_out[q * K + j] = id == RC_IDMAX ? -1 : id;
+        scores_out[q * K + j] = ls[j];
+    }
+}
+
+// Materialised path: packed rows of users [qb, qb + uc) x every item.
+__global__ __launch_bounds__(256) void rc_rows_kernel(const int32_t* __restrict__ users, int64_t qb, int64_t uc, int I,
+                                                      uint64_t* __restrict__ rows) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= uc * I) return;
+    const int64_t qq = p / I;
+    rows[p] = NCF_ROW_PACK(users[qb + qq], (int)(p - qq * I), 0);
+}
+
+// Materialised path: one wave per user selects from logits[uc][I].
+__global__ __launch_bounds__(RC_WAVES * 64) void rc_select_kernel(const float* __restrict__ logits,
+                                                                  const int32_t* __restrict__ users, int64_t qb,
+                                                                  int64_t uc, int I, int K,
+                                                                  const int64_t* __restrict__ seen_ptr,
+                                                                  const int32_t* __restrict__ seen_items,
+                                                                  int32_t* __restrict__ items_out,
+                                                                  float* __restrict__ scores_out) {
+    extern __shared__ f4 rc_smem4[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    float* const lsf = reinterpret_cast<float*>(rc_smem4) + wave * (2 * K + 64);
+    int* const lif = reinterpret_cast<int*>(lsf + K);
+    int* const scr = lif + K;
+    const int64_t qq = (int64_t)blockIdx.x * RC_WAVES + wave;
+    if (qq >= uc) return;
+    const int64_t q = qb + qq;
+    volatile float* ls = lsf;
+    volatile int* li = lif;
+    rc_list_init(ls, li, K, lane);
+    int64_t cur = 0, hi = 0;
+    if (seen_ptr != nullptr) {
+        const int u = users[q];
+        cur = seen_ptr[u];
+        hi = seen_ptr[u + 1];
+    }
+    for (int c0 = 0; c0 < I; c0 += RC_CH) {
+        unsigned long long seen = 0;
+        if (seen_ptr != nullptr) seen = rc_seen_mask(seen_items, &cur, hi, c0, scr, lane);
+        for (int tt = 0; tt < RC_CH / 16; ++tt) {
+            if (c0 + 16 * tt >= I) break;
+            const int row = 16 * tt + (lane & 15);
+            const int item = c0 + row;
+            const bool valid = lane < 16 && item < I && !((seen >> row) & 1ull);
+            const float z = valid ? logits[qq * I + item] : 0.f;
+            rc_feed(ls, li, K, z, item, valid, lane);
+        }
+    }
+    for (int j = lane; j < K; j += 64) {
+        const int id = li[j];
+        items_out[q * K + j] = id == RC_IDMAX ? -1 : id;
+        scores_out[q * K + j] = ls[j];
+    }
+}
+
+struct RcEntry {
+    int mode, F, L;
+    const void* fn;
+    int fixed, kp0, fp;  // LDS floats before the lists; padded Pi / Pu and Ag widths
+};
+
+template <int F, int L, int MODE>
+static RcEntry rc_make() {
+    using C = RcShape<F, L, MODE>;
+    return RcEntry{MODE, F, L, reinterpret_cast<const void*>(&rc_kernel<F, L, MODE>), C::FIXED, C::KP0, C::FP};
+}
+
+// The shapes of kernel_table (ncf_train.hip): every shape ncf_supported calls fused.
+static const RcEntry* rc_entry(const ncf_layout* lay) {
+    static const RcEntry table[] = {
+        rc_make<8, 1, NCF_MODEL_GMF>(),  rc_make<16, 1, NCF_MODEL_GMF>(),
+        rc_make<32, 1, NCF_MODEL_GMF>(), rc_make<64, 1, NCF_MODEL_GMF>(),
+#define NCF_RC_TOWER(F, L) rc_make<F, L, NCF_MODEL_MLP>(), rc_make<F, L, NCF_MODEL_NEUMF>()
+        NCF_RC_TOWER(8, 1),  NCF_RC_TOWER(8, 2),  NCF_RC_TOWER(8, 3),  NCF_RC_TOWER(8, 4),  NCF_RC_TOWER(16, 1),
+        NCF_RC_TOWER(16, 2), NCF_RC_TOWER(16, 3), NCF_RC_TOWER(32, 1), NCF_RC_TOWER(32, 2), NCF_RC_TOWER(64, 1),
+#undef NCF_RC_TOWER
+    };
+    const int Lk = lay->model_type == NCF_MODEL_GMF ? 1 : lay->num_layers;
+    for (const RcEntry& e : table)
+        if (e.mode == lay->model_type && e.F == lay->factor_num && e.L == Lk) return &e;
+    return nullptr;
+}
+
+static int64_t rc_al(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+
+// Launch shape of the fused kernel from the query size and the catalogue: 16-user tiles
+// from 256 queried users up (4-user tiles below), and as many item splits as bring the
+// grid to about four workgroups per compute unit.
+struct RcGeo {
+    int upw, nsplit, cps;
+    int64_t tiles;
+};
+static RcGeo rc_geometry(int64_t nq, int I) {
+    RcGeo G;
+    G.upw = nq >= 256 ? 4 : 1;
+    const int UT = RC_WAVES * G.upw;
+    G.tiles = (nq + UT - 1) / UT;
+    const int64_t nchunks = ((int64_t)I + RC_CH - 1) / RC_CH;
+    int64_t want = (1024 + G.tiles - 1) / G.tiles;
+    if (want > nchunks) want = nchunks;
+    if (want > 1024) want = 1024;
+    if (want < 1) want = 1;
+    G.cps = (int)((nchunks + want - 1) / want);
+    G.nsplit = (int)((nchunks + G.cps - 1) / G.cps);
+    return G;
+}
+
+static int64_t rc_lds_bytes(const RcEntry* e, const RcGeo& G, int K) {
+    const int UT = RC_WAVES * G.upw;
+    // fixed, 2 UT K and the 256 scratch ints are even counts of 4-byte words: cur is 8-byte aligned
+    return ((int64_t)e->fixed + 2 * UT * K + RC_WAVES * 64) * 4 + (int64_t)UT * 8;
+}
+
+struct RcFusedWs {
+    int64_t pi, pu, ag, ps, pid, total;
+};
+static RcFusedWs rc_fused_ws(const RcEntry* e, const ncf_layout* lay, int64_t nq, int K, const RcGeo& G) {
+    RcFusedWs w;
+    int64_t o = 0;
+    w.pi = o; o += rc_al((int64_t)lay->item_num * e->kp0 * 4);
+    w.pu = o; o += rc_al(nq * e->kp0 * 4);
+    w.ag = o; o += rc_al(nq * e->fp * 4);
+    w.ps = o; o += rc_al(nq * G.nsplit * K * 4);
+    w.pid = o; o += rc_al(nq * G.nsplit * K * 4);
+    w.total = o;
+    return w;
+}
+
+static int64_t rc_mat_users(const ncf_layout* lay, int64_t nq) {
+    int64_t uc = RC_MAT_PAIRS / lay->item_num;
+    if (uc < 1) uc = 1;
+    return uc < nq ? uc : nq;
+}
+
+struct RcMatWs {
+    int64_t rows, logits, fwd, fwd_bytes, total;
+};
+static RcMatWs rc_mat_ws(const ncf_layout* lay, int64_t nq) {
+    const int64_t pairs = rc_mat_users(lay, nq) * lay->item_num;
+    RcMatWs w;
+    int64_t o = 0;
+    w.rows = o; o += rc_al(pairs * 8);
+    w.logits = o; o += rc_al(pairs * 4);
+    w.fwd = o;
+    w.fwd_bytes = ncf_forward_workspace_bytes(lay, pairs);
+    o += rc_al(w.fwd_bytes);
+    w.total = o;
+    return w;
+}
+
+static bool rc_use_fused(const ncf_layout* lay) {
+    return g_rc_path != NCF_PATH_LAYERED &&
+           ncf_supported(lay->model_type, lay->factor_num, lay->num_layers) == NCF_PATH_FUSED && rc_entry(lay);
+}
+
+static int rc_ensure_lds(const void* fn, int64_t bytes) {
+    struct Slot { const void* fn; int64_t bytes; };
+    static Slot slots[64];
+    static int nslots = 0;
+    for (int i = 0; i < nslots; ++i)
+        if (slots[i].fn == fn && slots[i].bytes >= bytes) return NCF_OK;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+        return NCF_E_LAUNCH;
+    for (int i = 0; i < nslots; ++i)
+        if (slots[i].fn == fn) { slots[i].bytes = bytes; return NCF_OK; }
+    if (nslots < 64) slots[nslots++] = Slot{fn, bytes};
+    return NCF_OK;
+}
+
+static int rc_status() { return hipGetLastError() == hipSuccess ? NCF_OK : NCF_E_LAUNCH; }
+
+}  // namespace ncf
+
+using namespace ncf;
+
+extern "C" {
+
+int ncf_debug_set_recommend_path(int path) {
+    if (path != 0 && path != NCF_PATH_LAYERED) return NCF_E_ARG;
+    g_rc_path = path;
+    return NCF_OK;
+}
+
+int64_t ncf_recommend_workspace_bytes(const ncf_layout* lay, int64_t n_users, int top_k) {
+    if (!lay || n_users < 0 || top_k < 1 || top_k > RC_MAXK || lay->item_num <= 0) return -1;
+    if (!ncf_supported(lay->model_type, lay->factor_num, lay->num_layers)) return -1;
+    if (n_users == 0) return 0;
+    if (rc_use_fused(lay))
+        return rc_fused_ws(rc_entry(lay), lay, n_users, top_k, rc_geometry(n_users, lay->item_num)).total;
+    return rc_mat_ws(lay, n_users).total;
+}
+
+int ncf_recommend(const ncf_layout* lay, const float* params, const int32_t* users, int64_t n_users, int top_k,
+                  const int64_t* seen_ptr, const int32_t* seen_items, int32_t* items_out, float* scores_out,
+                  void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!lay || n_users < 0 || top_k < 1 || top_k > RC_MAXK) return NCF_E_ARG;
+    if (n_users == 0) return NCF_OK;
+    if (!params || !users || !items_out || !scores_out || !workspace) return NCF_E_ARG;
+    if ((seen_ptr == nullptr) != (seen_items == nullptr)) return NCF_E_ARG;
+    if (!ncf_supported(lay->model_type, lay->factor_num, lay->num_layers)) return NCF_E_UNSUPPORTED;
+    if (workspace_bytes < ncf_recommend_workspace_bytes(lay, n_users, top_k)) return NCF_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    const int I = lay->item_num, K = top_k;
+
+    if (rc_use_fused(lay)) {
+        const RcEntry* e = rc_entry(lay);
+        const RcGeo G = rc_geometry(n_users, I);
+        const RcFusedWs W = rc_fused_ws(e, lay, n_users, K, G);
+        const int64_t lds = rc_lds_bytes(e, G, K);
+        if (lds > RC_LDS_LIMIT) return NCF_E_UNSUPPORTED;
+        if (rc_ensure_lds(e->fn, lds) != NCF_OK) return NCF_E_LAUNCH;
+        RcArgs a;
+        memset(&a, 0, sizeof(a));
+        a.lay = *lay;
+        a.params = params;
+        a.users = users;
+        a.nq = n_users;
+        a.K = K;
+        a.seen_ptr = seen_ptr;
+        a.seen_items = seen_items;
+        a.Pi = reinterpret_cast<float*>(ws + W.pi);
+        a.Pu = reinterpret_cast<float*>(ws + W.pu);
+        a.Ag = reinterpret_cast<float*>(ws + W.ag);
+        a.part_s = reinterpret_cast<float*>(ws + W.ps);
+        a.part_i = reinterpret_cast<int32_t*>(ws + W.pid);
+        a.nsplit = G.nsplit;
+        a.cps = G.cps;
+        a.upw = G.upw;
+        const int64_t nproj = ((int64_t)I + n_users) * e->kp0 + n_users * e->fp;
+        hipLaunchKernelGGL(rc_proj_kernel, dim3((unsigned)((nproj + 255) / 256)), dim3(256), 0, st, *lay, params,
+                           users, n_users, e->kp0, e->fp, const_cast<float*>(a.Pi), const_cast<float*>(a.Pu),
+                           const_cast<float*>(a.Ag));
+        void* args[] = {&a};
+        if (hipLaunchKernel(e->fn, dim3((unsigned)G.tiles, (unsigned)G.nsplit), dim3(RC_WAVES * 64), args, (size_t)lds,
+                            st) != hipSuccess)
+            return NCF_E_LAUNCH;
+        hipLaunchKernelGGL(rc_merge_kernel, dim3((unsigned)((n_users + RC_WAVES - 1) / RC_WAVES)), dim3(RC_WAVES * 64),
+                           (size_t)RC_WAVES * 2 * K * 4, st, a.part_s, a.part_i, n_users, G.nsplit, K, items_out,
+                           scores_out);
+        return rc_status();
+    }
+
+    const RcMatWs W = rc_mat_ws(lay, n_users);
+    const int64_t ucmax = rc_mat_users(lay, n_users);
+    uint64_t* rows = reinterpret_cast<uint64_t*>(ws + W.rows);
+    float* logits = reinterpret_cast<float*>(ws + W.logits);
+    for (int64_t qb = 0; qb < n_users; qb += ucmax) {
+        const int64_t uc = n_users - qb < ucmax ? n_users - qb : ucmax;
+        const int64_t pairs = uc * I;
+        hipLaunchKernelGGL(rc_rows_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, users, qb, uc, I,
+                           rows);
+        const int rc = ncf_forward(lay, params, rows, pairs, logits, W.fwd_bytes ? ws + W.fwd : nullptr, W.fwd_bytes,
+                                   stream);
+        if (rc != NCF_OK) return rc;
+        hipLaunchKernelGGL(rc_select_kernel, dim3((unsigned)((uc + RC_WAVES - 1) / RC_WAVES)), dim3(RC_WAVES * 64),
+                           (size_t)RC_WAVES * (2 * K + 64) * 4, st, logits, users, qb, uc, I, K, seen_ptr, seen_items,
+                           items_out, scores_out);
+    }
+    return rc_status();
+}
+
+}  // extern "C"

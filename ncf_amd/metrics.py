@@ -113,3 +113,29 @@ def _metrics_cpu(model, test_loader, top_k):
             ndcg = 1.0 / np.log2(index + 2)
         NDCG.append(ndcg)
     return HR, NDCG
+
+
+def hr_ndcg_from_topk(items, gt_items):
+    """Per-user HR (int) and NDCG (float) lists from ranked item ids [Q, k] and the held-out
+    item of each row: metrics()'s formulas (hit if gt is in the top k, 1 / log2(pos + 2))."""
+    items = np.asarray(items)
+    gt = np.asarray(gt_items).reshape(-1, 1)
+    hit = items == gt
+    any_hit = hit.any(axis=1)
+    pos = hit.argmax(axis=1)
+    ndcg = np.where(any_hit, 1.0 / np.log2(pos + 2.0), 0.0)
+    return [int(h) for h in any_hit], [float(x) for x in ndcg]
+
+
+def full_rank_metrics(model, users, gt_items, top_k, exclude=None):
+    """Full-ranking HR@K / NDCG@K: each user's held-out item ranked against the whole
+    catalogue (``model.recommend``; ``exclude`` as there, usually the training
+    positives) instead of the 99 sampled negatives of ``metrics()``.  Per-user lists."""
+    users = np.asarray(users).reshape(-1)
+    gt = np.asarray(gt_items).reshape(-1)
+    if users.size != gt.size:
+        raise ValueError("users and gt_items must have equal length")
+    if users.size == 0:
+        return [], []
+    items, _ = model.recommend(torch.as_tensor(users.astype(np.int64)), top_k, exclude)
+    return hr_ndcg_from_topk(items.cpu().numpy(), gt)

@@ -135,3 +135,70 @@ class NCF(nn.Module):
             mlp = self.MLP_layers(torch.cat((self.embed_user_MLP(user), self.embed_item_MLP(item)), -1))
             output = torch.cat((gmf, mlp), -1)
         return self.predict_layer(output).view(-1)
+
+    # ---------------------------------------------------------------- recommend
+    def recommend(self, users, k=10, exclude=None):
+        """The k best items of every queried user over the whole catalogue:
+        ``(items int64 [Q, k], scores float32 [Q, k])`` on the model's device.  Scores
+        are ``forward(u, i)`` in eval mode (dropout never applies, whatever
+        ``self.training``); order: score descending, then item id ascending.
+        ``exclude``: items to leave out per user -- an ``ops.SeenCSR``
+        (``ops.seen_csr``), the DOK ``train_mat`` of ``load_all`` or a
+        ``(users, items)`` pair of arrays.  A user with fewer than k eligible items
+        gets item -1 and score -inf in the trailing slots.  1 <= k <= 128.
+
+        On a HIP device this is ``ncf_recommend`` (the fused score-and-select kernel);
+        a CPU model runs the same contract with stock torch ops."""
+        from . import ops
+        k = ops.check_top_k(k)
+        dev = self.embed_user_GMF.weight.device
+        seen = ops.as_seen(exclude, self, dev)
+        if dev.type == "cuda":
+            items, scores = ops.recommend(self, users, k, seen)
+            return items.to(torch.int64), scores
+        return self._recommend_cpu(users, k, seen)
+
+    def _logits_eval(self, user, item):
+        """forward() with the tower's Dropout modules skipped (eval semantics)."""
+        def tower(x):
+            for lin in self.linear_layers():
+                x = torch.relu(lin(x))
+            return x
+        if self.model_type == "GMF":
+            output = self.embed_user_GMF(user) * self.embed_item_GMF(item)
+        elif self.model_type == "MLP":
+            output = tower(torch.cat((self.embed_user_MLP(user), self.embed_item_MLP(item)), -1))
+        else:
+            gmf = self.embed_user_GMF(user) * self.embed_item_GMF(item)
+            mlp = tower(torch.cat((self.embed_user_MLP(user), self.embed_item_MLP(item)), -1))
+            output = torch.cat((gmf, mlp), -1)
+        return self.predict_layer(output).view(-1)
+
+    @torch.no_grad()
+    def _recommend_cpu(self, users, k, seen, chunk_pairs=1 << 20):
+        u = torch.as_tensor(users).to(torch.int64).view(-1)
+        if u.numel() and (int(u.min()) < 0 or int(u.max()) >= self.user_num):
+            raise IndexError("index out of range in self (user id)")
+        n_items = self.item_num
+        q = u.numel()
+        out_i = torch.full((q, k), -1, dtype=torch.int64)
+        out_s = torch.full((q, k), float("-inf"), dtype=torch.float32)
+        all_items = torch.arange(n_items, dtype=torch.int64)
+        step = max(1, chunk_pairs // n_items)
+        for b in range(0, q, step):
+            uc = u[b:b + step]
+            c = uc.numel()
+            s = self._logits_eval(uc.repeat_interleave(n_items), all_items.repeat(c)).view(c, n_items)
+            eligible = torch.full((c,), n_items, dtype=torch.int64)
+            if seen is not None:
+                lo, hi = seen.ptr[uc], seen.ptr[uc + 1]
+                eligible -= hi - lo
+                for r in range(c):
+                    s[r, seen.items[int(lo[r]):int(hi[r])].to(torch.int64)] = float("-inf")
+            # stable: equal scores keep ascending item ids; excluded items sort last
+            val, idx = torch.sort(s, dim=1, descending=True, stable=True)
+            m = min(k, n_items)
+            keep = torch.arange(m).unsqueeze(0) < eligible.unsqueeze(1)
+            out_i[b:b + c, :m] = torch.where(keep, idx[:, :m], torch.full_like(idx[:, :m], -1))
+            out_s[b:b + c, :m] = torch.where(keep, val[:, :m], torch.full_like(val[:, :m], float("-inf")))
+        return out_i, out_s

@@ -13,6 +13,7 @@ module's ``state_dict`` / stock optimizers keep working.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 
 import numpy as np
@@ -379,3 +380,125 @@ def ncf_forward(model, user, item):
     if drop is not None:
         return _dropout_logits(model, rows, drop)
     return forward_logits(flat, lay, rows, ws_owner=model)
+
+
+# ---------------------------------------------------------------------------
+# Full-catalogue top-K recommendation (include/ncf_hip.h ncf_recommend, ABI 20)
+MAX_TOP_K = 128  # ncf_recommend's limit
+
+
+class SeenCSR(collections.namedtuple("SeenCSR", "ptr items")):
+    """Items to leave out per user: ptr int64 [user_num + 1] indexed by user id, items
+    int32, ascending and unique inside a user (the seen_ptr / seen_items of ncf_recommend)."""
+    __slots__ = ()
+
+
+def _is_dok(x):
+    return hasattr(x, "keys") and hasattr(x, "shape") and not isinstance(x, (np.ndarray, torch.Tensor))
+
+
+def seen_csr(users, items=None, user_num=None, device=None, item_num=None):
+    """SeenCSR of the (user, item) pairs: sorted, de-duplicated, range-checked
+    (IndexError on a user id outside [0, user_num) or an item id outside [0, item_num)).
+    `users` may also be the scipy DOK ``train_mat`` that ``load_all`` returns (its keys
+    are the pairs; user_num / item_num default to its shape)."""
+    if _is_dok(users):
+        mat = users
+        ks = np.array(list(mat.keys()), dtype=np.int64).reshape(-1, 2)
+        u, i = ks[:, 0], ks[:, 1]
+        if user_num is None:
+            user_num = int(mat.shape[0])
+        if item_num is None:
+            item_num = int(mat.shape[1])
+    else:
+        if items is None:
+            raise ValueError("seen_csr: items is required with user / item arrays")
+        u = np.asarray(users.cpu() if isinstance(users, torch.Tensor) else users).astype(np.int64).reshape(-1)
+        i = np.asarray(items.cpu() if isinstance(items, torch.Tensor) else items).astype(np.int64).reshape(-1)
+        if u.size != i.size:
+            raise ValueError("seen_csr: users and items must have equal length")
+    if user_num is None:
+        raise ValueError("seen_csr: user_num is required")
+    user_num = int(user_num)
+    if u.size and (int(u.min()) < 0 or int(u.max()) >= user_num):
+        raise IndexError("index out of range in self (user id)")
+    hi = (1 << 31) - 1 if item_num is None else int(item_num)
+    if i.size and (int(i.min()) < 0 or int(i.max()) >= hi):
+        raise IndexError("index out of range in self (item id)")
+    key = np.unique(u * (1 << 32) + i)  # sorted by (user, item), duplicates dropped
+    su = key >> 32
+    ptr = np.zeros(user_num + 1, dtype=np.int64)
+    np.cumsum(np.bincount(su, minlength=user_num), out=ptr[1:])
+    dev = torch.device("cpu") if device is None else torch.device(device)
+    return SeenCSR(torch.from_numpy(ptr).to(dev), torch.from_numpy((key & 0xFFFFFFFF).astype(np.int32)).to(dev))
+
+
+def as_seen(exclude, model, device):
+    """None, a SeenCSR, a DOK matrix or a (users, items) pair -> SeenCSR on `device` (or None)."""
+    if exclude is None:
+        return None
+    if isinstance(exclude, SeenCSR):
+        if exclude.ptr.numel() != model.user_num + 1 or exclude.ptr.dtype != torch.int64 \
+                or exclude.items.dtype != torch.int32:
+            raise ValueError("exclude: SeenCSR needs ptr int64 [user_num + 1] and int32 items")
+        return SeenCSR(exclude.ptr.to(device).contiguous(), exclude.items.to(device).contiguous())
+    if _is_dok(exclude):
+        return seen_csr(exclude, None, model.user_num, device, model.item_num)
+    u, i = exclude
+    return seen_csr(u, i, model.user_num, device, model.item_num)
+
+
+def check_top_k(k):
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_TOP_K:
+        raise ValueError(f"top-k must be an integer in [1, {MAX_TOP_K}], got {k!r}")
+    return int(k)
+
+
+@contextlib.contextmanager
+def _recommend_materialised():
+    """Tests: ncf_recommend through its materialised path whatever the shape."""
+    L.check(L.hip().ncf_debug_set_recommend_path(L.PATH_LAYERED), "ncf_debug_set_recommend_path")
+    try:
+        yield
+    finally:
+        L.hip().ncf_debug_set_recommend_path(0)
+
+
+def recommend_into(flat, lay, users_i32, k, seen, items_out, scores_out, ws):
+    """One ncf_recommend call on the current stream into preallocated tensors
+    (capturable: nothing is allocated or synchronised)."""
+    dev = flat.device
+    L.check(L.hip().ncf_recommend(L.ctypes.byref(lay), flat.data_ptr(), users_i32.data_ptr(), users_i32.numel(), k,
+                                  None if seen is None else seen.ptr.data_ptr(),
+                                  None if seen is None else seen.items.data_ptr(),
+                                  items_out.data_ptr(), scores_out.data_ptr(),
+                                  None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
+                                  L.stream_ptr(dev)), "ncf_recommend")
+
+
+def recommend_workspace(lay, n_users, k, owner, dev):
+    need = int(L.hip().ncf_recommend_workspace_bytes(L.ctypes.byref(lay), int(n_users), int(k)))
+    if need < 0:
+        raise ValueError("ncf_recommend_workspace_bytes failed")
+    return _ws(owner, "_ncf_rec_ws", need, dev)
+
+
+def recommend(model, users, k, seen=None):
+    """(items int32 [Q, k], scores float32 [Q, k]) of a HIP-resident model: the k best
+    items of every queried user over the whole catalogue, score descending then item id
+    ascending, `seen` (a SeenCSR on the device) left out, -1 / -inf in unfilled slots."""
+    k = check_top_k(k)
+    flat, lay = ensure_flat(model)
+    dev = flat.device
+    u = _as_i32(users, dev).view(-1)
+    q = u.numel()
+    items = torch.empty((q, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((q, k), dtype=torch.float32, device=dev)
+    if q == 0:
+        return items, scores
+    lo, hi = torch.stack([u.min(), u.max()]).tolist()
+    if lo < 0 or hi >= model.user_num:
+        raise IndexError("index out of range in self (user id)")
+    ws = recommend_workspace(lay, q, k, model, dev)
+    recommend_into(flat, lay, u, k, seen, items, scores, ws)
+    return items, scores

@@ -134,6 +134,28 @@ class Trainer:
         hr, nd = self._evaluate_device(top_k)
         return hr.cpu().tolist(), nd.double().cpu().tolist()
 
+    def evaluate_full(self, top_k=None):
+        """Full-ranking HR@K / NDCG@K (ncf_amd.metrics.full_rank_metrics): every test
+        user's held-out item -- the first row of each test batch, as metrics() defines the
+        ground truth -- ranked against the whole catalogue with the training positives
+        left out (the training set's train_mat, or its positives when that is None).
+        Per-user lists.  Draws nothing from the torch generator."""
+        from .metrics import full_rank_metrics
+        k = self.top_k if top_k is None else int(top_k)
+        if self._test is None:  # a generic loader is iterated once: keep its base_seed draw out
+            state = torch.get_rng_state()
+            self._test_arrays()
+            torch.set_rng_state(state)
+        u, i, bs = self._test_arrays()
+        if getattr(self, "_seen", None) is None:
+            mat = getattr(self.ds, "train_mat", None)
+            if mat is not None and hasattr(mat, "keys") and hasattr(mat, "shape"):
+                self._seen = ops.seen_csr(mat, None, int(self.model.user_num), self.device, int(self.model.item_num))
+            else:
+                self._seen = ops.seen_csr(self.ds._ps_u, self.ds._ps_i, int(self.model.user_num), self.device,
+                                          int(self.model.item_num))
+        return full_rank_metrics(self.model, u[::bs], i[::bs], k, self._seen)
+
     def train_epoch(self):
         rows = self._epoch_stream()
         self.engine.set_epoch_stream(rows, self.batch_size, checked=True)  # ids checked on the host

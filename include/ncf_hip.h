@@ -21,7 +21,8 @@
 extern "C" {
 #endif
 
-/* 20: full-catalogue top-K inference: ncf_recommend_workspace_bytes, ncf_recommend,
+/* 21: pairwise (BPR) training: NCF_DZ_BPR of ncf_train_step, ncf_build_pair_stream.
+ * 20: full-catalogue top-K inference: ncf_recommend_workspace_bytes, ncf_recommend,
  * ncf_debug_set_recommend_path.
  * 19: NCF_LAYOUT_FACT_IN_ADAM (0x20) removed -- measured slower than the two launches it
  * replaced; the bit is retired (NCF_LAYOUT_RETIRED_0X20: rejected by
@@ -37,7 +38,7 @@ extern "C" {
  * 15: ncf_layout.flags gains the fused step's workgroup geometry (NCF_LAYOUT_GEO_*) and
  * NCF_LAYOUT_FACT_DEFER_DX; new ncf_adam_step_fact, ncf_prepare_epoch2
  * (NCF_PREP_CANONICAL), ncf_probe_gather_scatter, ncf_debug_set_geometry. */
-#define NCF_ABI_VERSION 20
+#define NCF_ABI_VERSION 21
 
 #define NCF_OK 0
 #define NCF_E_UNSUPPORTED (-1) /* (model_type, factor_num, num_layers) has no compiled kernel */
@@ -65,6 +66,8 @@ extern "C" {
 #define NCF_DZ_BCE 0    /* fused nn.BCEWithLogitsLoss() (mean) from labels (train_neumf.py:86,113) */
 #define NCF_DZ_DLOGIT 1 /* upstream dL/dlogit given per row (autograd backward of NCF.forward) */
 #define NCF_DZ_KD 2     /* distillation: w_task * BCE + w_resp * response term (ncf_train_step_kd) */
+#define NCF_DZ_BPR 3    /* pairwise ranking loss over (user, item+, item-) triples (since ABI 21; the reference
+                           has no pairwise objective: its only loss is train_neumf.py:86) */
 
 /* Flat parameter buffer layout, offsets in floats.  Order and shapes follow the
  * reference state_dict (models.py:11-34): embed_user_GMF [U,f], embed_item_GMF [I,f],
@@ -169,6 +172,19 @@ int64_t ncf_slab_stride(const ncf_layout *lay);
  * grads by ncf_reduce_slab.
  * dz_mode NCF_DZ_BCE: the label is bit 63 of the row, `dlogit` is ignored (may be NULL).
  * dz_mode NCF_DZ_DLOGIT: dlogit[row] holds dL/dlogit per row (same indexing as rows).
+ * dz_mode NCF_DZ_BPR (since ABI 21): rows 2k and 2k + 1 of the epoch stream are one triple
+ * -- row 2k is (u, i+) with label bit 1, row 2k + 1 is (u, i-) with label bit 0, both with
+ * the same user, or both padding (user -1; ncf_build_pair_stream writes such a stream).
+ * With d_k = z(2k) - z(2k + 1) and T = gb / 2, gb being the rows of this global batch
+ * counted as in the BCE mode (last batch partial, padding rows included):
+ *   loss = sum_k softplus(-d_k) / T,  dL/dz(2k) = (sigmoid(d_k) - 1) / T = -dL/dz(2k + 1);
+ * padding pairs add nothing.  The loss lands in the same loss slot, logits_out still
+ * receives every row's z, `dlogit` is ignored (may be NULL).  world != 1 or an odd
+ * batch_global: NCF_E_ARG (a rank slice or an odd batch could split a pair); the stream
+ * length ctl->n_total must be even (the caller's check: it lives on the device).
+ * ncf_train_step_ais refuses the mode (NCF_E_ARG); ncf_train_step_kd has no mode argument.
+ * On the layered path the pairwise kernels take the rows in stream order (user_order is
+ * not used: a pair stream is not grouped by item).
  * logits_out (optional, may be NULL): per-row logits of this rank's rows.
  * user_order (optional, may be NULL; since ABI 12): ncf_user_order of the same rows,
  * batch_global and world.  Where ncf_uses_user_order(lay), the step then sums the
@@ -589,6 +605,20 @@ int ncf_randperm(const uint32_t *words, int64_t n, int64_t *perm, void *workspac
                  void *stream);
 int ncf_build_rows(const int32_t *pos_users, const int32_t *pos_items, int64_t n_pos, const int32_t *neg, int num_ng,
                    uint64_t *rows_out, void *stream);
+
+/*
+ * Pair stream of the pairwise mode (NCF_DZ_BPR; since ABI 21): S = n_pos * num_ng triples
+ * (positive p with each of its num_ng sampled negatives neg[p * num_ng ..), the neg layout
+ * of ncf_build_rows) in the order perm (NULL: identity) -- for k < S, t = perm ? perm[k] : k,
+ * p = t / num_ng:
+ *   rows_out[2k]     = NCF_ROW_PACK(pos_users[p], pos_items[p], 1)
+ *   rows_out[2k + 1] = NCF_ROW_PACK(pos_users[p], neg[t], 0)
+ * i.e. DataLoader(shuffle=True) over a dataset of the S triples.  One kernel, one 16-byte
+ * store per triple (rows_out 16-byte aligned, else NCF_E_ARG); S == 0 returns NCF_OK.
+ */
+int ncf_build_pair_stream(const int32_t *pos_users, const int32_t *pos_items, int64_t n_pos,
+                          const int32_t *neg, int num_ng, const int64_t *perm,
+                          uint64_t *rows_out, void *stream);
 
 /*
  * HR@K / NDCG@K per DataLoader batch (metrics.py:4-25): batches of `batch`

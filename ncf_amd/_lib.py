@@ -29,7 +29,8 @@ NCF_E_ARG = -2
 NCF_E_LAUNCH = -3
 MODEL_GMF, MODEL_MLP, MODEL_NEUMF = 0, 1, 2
 DZ_BCE, DZ_DLOGIT, DZ_KD = 0, 1, 2
-ABI_VERSION = 20  # include/ncf_hip.h NCF_ABI_VERSION
+DZ_BPR = 3  # pairwise ranking loss over (user, item+, item-) triples (ncf_train_step, ABI 21)
+ABI_VERSION = 21  # include/ncf_hip.h NCF_ABI_VERSION
 PATH_FUSED, PATH_LAYERED = 1, 2  # ncf_supported()
 LAYOUT_PER_ROW_L0, LAYOUT_WG_SHIFT, LAYOUT_WG_MASK = 0x1, 8, 0xFFF  # ncf_layout.flags (ncf_layout_tune)
 LAYOUT_LAYERED = 0x2  # ncf_layout.flags: training on the layered path even where a fused kernel exists
@@ -140,6 +141,7 @@ _HIP_PROTOS = {
     "ncf_randperm_workspace": (c_i64, [c_i64]),
     "ncf_randperm": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "ncf_build_rows": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, ctypes.c_int, c_vp, c_vp]),
+    "ncf_build_pair_stream": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
     "ncf_user_order": (ctypes.c_int, [c_vp, c_i64, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "ncf_uses_user_order": (ctypes.c_int, [c_vp]),
     "ncf_touched_bytes": (c_i64, [c_i64, c_i64, ctypes.c_int, ctypes.c_int]),

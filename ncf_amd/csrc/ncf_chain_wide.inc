@@ -205,6 +205,7 @@ __global__ __launch_bounds__(256) void lyr_wc_prep_kernel(const float* __restric
     *reinterpret_cast<uint4*>(dst + img_off(ph.mt, ksl, 2, t)) = lo;
 }
 
+template <bool BPR = false>  // BPR: the pairwise (NCF_DZ_BPR) instantiation
 __global__ __launch_bounds__(wc::NT) void lyr_wide_chain_kernel(LyrArgs a, const float* __restrict__ P, ChainBufs o,
                                                                 const char* __restrict__ img, int64_t R) {
     using namespace wc;
@@ -383,7 +384,13 @@ WC_BEGIN();
         const float z = zp + bp;
         if (valid && g == 0 && a.logits_out != nullptr) a.logits_out[m] = z;
         float dz = 0.f;
-        if (valid) {
+        if constexpr (BPR) {
+            // pairwise (BPR), as in lyr_step_chain_kernel: ROWS (128) and each wave's 16-row
+            // slice are even, so a pair never straddles a tile and the partner's z is in
+            // lane l ^ 1; both rows of a pair are valid or both padding (stream contract).
+            static_assert(ROWS % 2 == 0, "a BPR pair must not straddle a row tile");
+            dz = bpr_dz(z, __shfl_xor(z, 1, 64), rw, valid, g == 0, s.gb, aL);
+        } else if (valid) {
             if (a.dz_mode == NCF_DZ_BCE) {
                 const float y = (float)(uint32_t)(rw >> 63);
                 dz = (sigmoidf_(z) - y) / s.gb;
@@ -587,7 +594,9 @@ static bool launch_wide_chain(const LyrArgs& a, const float* P, const ChainBufs&
     if (DM != wc::DM || L != wc::L || img == nullptr || !wide_chain_enabled()) return false;
     static bool attr = false;
     if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&lyr_wide_chain_kernel),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&lyr_wide_chain_kernel<false>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 2 * wc::CHUNK) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&lyr_wide_chain_kernel<true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 2 * wc::CHUNK) != hipSuccess)
             return false;
         attr = true;
@@ -596,7 +605,11 @@ static bool launch_wide_chain(const LyrArgs& a, const float* P, const ChainBufs&
     int64_t grid = (R + wc::ROWS - 1) / wc::ROWS;
     if (grid > 256) grid = 256;  // one 8-wave block per CU, persistent over the tiles
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(lyr_wide_chain_kernel, dim3((unsigned)grid), dim3(wc::NT), 2 * wc::CHUNK, st, a, P, o,
-                       (const char*)img, R);
+    if (a.dz_mode == NCF_DZ_BPR)
+        hipLaunchKernelGGL(lyr_wide_chain_kernel<true>, dim3((unsigned)grid), dim3(wc::NT), 2 * wc::CHUNK, st, a, P, o,
+                           (const char*)img, R);
+    else
+        hipLaunchKernelGGL(lyr_wide_chain_kernel<false>, dim3((unsigned)grid), dim3(wc::NT), 2 * wc::CHUNK, st, a, P,
+                           o, (const char*)img, R);
     return true;
 }

@@ -111,6 +111,23 @@ __global__ __launch_bounds__(EP_THREADS) void build_rows_kernel(const int32_t* _
     }
 }
 
+// One triple per thread: rows 2k (positive) and 2k + 1 (its negative) in one 16-byte store.
+struct alignas(16) RowPair {
+    uint64_t pos, neg;
+};
+__global__ __launch_bounds__(EP_THREADS) void build_pair_stream_kernel(const int32_t* __restrict__ pu,
+                                                                       const int32_t* __restrict__ pi, int64_t S, int ng,
+                                                                       const int32_t* __restrict__ neg,
+                                                                       const int64_t* __restrict__ perm,
+                                                                       RowPair* __restrict__ out) {
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < S; k += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t t = perm != nullptr ? perm[k] : k;
+        const int64_t p = t / ng;
+        const int u = pu[p];
+        out[k] = RowPair{NCF_ROW_PACK(u, pi[p], 1), NCF_ROW_PACK(u, neg[t], 0)};
+    }
+}
+
 struct FyLayout {
     uint32_t *keys, *keys_sorted;
     int32_t *steps_sorted, *P, *K;
@@ -181,6 +198,17 @@ int ncf_build_rows(const int32_t* pos_users, const int32_t* pos_items, int64_t n
     if (n == 0) return NCF_OK;
     hipLaunchKernelGGL(build_rows_kernel, dim3(ep_grid(n, 8192)), dim3(EP_THREADS), 0, (hipStream_t)stream, pos_users,
                        pos_items, n_pos, neg, num_ng, rows_out);
+    return ep_status();
+}
+
+int ncf_build_pair_stream(const int32_t* pos_users, const int32_t* pos_items, int64_t n_pos, const int32_t* neg,
+                          int num_ng, const int64_t* perm, uint64_t* rows_out, void* stream) {
+    if (!pos_users || !pos_items || !rows_out || n_pos < 0 || num_ng < 0 || (num_ng > 0 && !neg)) return NCF_E_ARG;
+    if (reinterpret_cast<uintptr_t>(rows_out) & 15) return NCF_E_ARG;
+    const int64_t S = n_pos * num_ng;
+    if (S == 0) return NCF_OK;
+    hipLaunchKernelGGL(build_pair_stream_kernel, dim3(ep_grid(S, 8192)), dim3(EP_THREADS), 0, (hipStream_t)stream,
+                       pos_users, pos_items, S, num_ng, neg, perm, reinterpret_cast<RowPair*>(rows_out));
     return ep_status();
 }
 

@@ -166,4 +166,12 @@ struct KernelEntry {
 
 const KernelEntry* kernel_table(int* n);
 
+// The pairwise (NCF_DZ_BPR) instantiations, entry k for kernel_table()[k]
+// (ncf_train_bpr.hip): the two-launch training step only, per geometry.
+struct BprEntry {
+    const void* train[NGEO];
+    const void* train_fact[NGEO];
+};
+const BprEntry* kernel_table_bpr(int* n);
+
 }  // namespace ncf

@@ -62,6 +62,22 @@ __device__ __forceinline__ Sel select_rows(const LyrArgs& a) {
     return Sel{b0 + lo, hi - lo, (float)gb};
 }
 
+// dL/dz of one row of a pairwise (NCF_DZ_BPR) triple: z this row's logit, zo its partner's
+// (rows 2k / 2k + 1; the label bit 63 of `rw` says which this is), with d = z(2k) - z(2k+1)
+// -- the same bits from both rows -- and T = gb / 2 triples:
+//   dL/dz(2k) = (sigmoid(d) - 1) / T = -dL/dz(2k+1);  loss += softplus(-d) / T from the
+// label-1 row's `lead` lane only.  Invalid (padding) rows give 0.
+__device__ __forceinline__ float bpr_dz(float z, float zo, uint64_t rw, bool valid, bool lead, float gb,
+                                        float& loss) {
+    if (!valid) return 0.f;
+    const float T = 0.5f * gb;
+    const bool pos = (rw >> 63) != 0;
+    const float d = pos ? z - zo : zo - z;
+    const float sg = (sigmoidf_(d) - 1.0f) / T;
+    if (lead && pos) loss += bce_loss(d, 1.0f) / T;
+    return pos ? sg : -sg;
+}
+
 // Dropout of the input of tower layer k (training steps with lay.dropout > 0):
 // element (epoch-stream row r, column c) is multiplied by 1 / (1 - p) when kept,
 // else 0 (ncf_hip.h ncf_dropout_hash).  Off for forward-only launches (ctl null).
@@ -1176,7 +1192,7 @@ constexpr int CNT = NCF_CHAIN_NT, CROWS = CNT / 4;  // threads per block, rows p
 // D_0 row at its position in the user order, so the user-side walk
 // (the walk blocks of lyr_bwd_w_multi_kernel) reads D_0 sequentially.  Without it,
 // D_0 in row order and lyr_scatter0_kernel does all three.
-template <int DM, int L, bool UORD>
+template <int DM, int L, bool UORD, bool BPR = false>
 __global__ __launch_bounds__(CNT, 2) void lyr_step_chain_kernel(LyrArgs a, const float* __restrict__ P, ChainBufs o,
                                                                 int64_t R) {
     using C_ = ChainShape<DM, L>;
@@ -1331,7 +1347,14 @@ __global__ __launch_bounds__(CNT, 2) void lyr_step_chain_kernel(LyrArgs a, const
         const float z = zp + bp;
         if (valid && g == 0 && a.logits_out != nullptr) a.logits_out[m] = z;
         float dz = 0.f;
-        if (valid) {
+        if constexpr (BPR) {
+            // pairwise (BPR): rows 2k (label 1) / 2k + 1 (label 0) are one triple.  The row
+            // tile (CROWS, 16 rows per wave, lane c = row) is even, so a pair never
+            // straddles a tile: the partner's z is in lane l ^ 1 -- one cross-lane
+            // exchange.  Both rows of a pair are valid or both padding (stream contract).
+            static_assert(CROWS % 2 == 0, "a BPR pair must not straddle a row tile");
+            dz = bpr_dz(z, __shfl_xor(z, 1, 64), rw, valid, g == 0, s.gb, aL);
+        } else if (valid) {
             if (a.dz_mode == NCF_DZ_BCE) {
                 const float y = (float)(uint32_t)(rw >> 63);
                 dz = (sigmoidf_(z) - y) / s.gb;
@@ -1558,7 +1581,10 @@ static bool launch_step_chain(const LyrArgs& a, const float* P, const ChainBufs&
     if (grid < 1) grid = 1;
 #define NCF_CHAIN(D, LL)                                                                                   \
     if (DM == D && L == LL) {                                                                              \
-        if (a.uorder)                                                                                      \
+        if (a.dz_mode == NCF_DZ_BPR) /* pairwise: rows in stream order (no user order) */                  \
+            hipLaunchKernelGGL((lyr_step_chain_kernel<D, LL, false, true>), dim3((unsigned)grid), dim3(CNT), 0, st, \
+                               a, P, o, R);                                                                \
+        else if (a.uorder)                                                                                 \
             hipLaunchKernelGGL((lyr_step_chain_kernel<D, LL, true>), dim3((unsigned)grid), dim3(CNT), 0, st, a, \
                                P, o, R);                                                                   \
         else                                                                                               \
@@ -1721,7 +1747,7 @@ __device__ __forceinline__ void user_walk_body(const LyrArgs& a, const float* __
 // loss: registers -> LDS -> one atomic per value per block, into slab row
 // blockIdx % lyr_slab_rows.
 constexpr int PR_ROWS = 8;  // NS <= 4: F <= 256 (LYR_MAX_FACTOR)
-template <bool TRAIN, int NS>
+template <bool TRAIN, int NS, bool BPR = false>
 __global__ __launch_bounds__(GNT) void lyr_predict_kernel(LyrArgs a, const float* __restrict__ HL,
                                                           float* __restrict__ Dout, int64_t R, int G) {
     extern __shared__ float red[];  // [P + 2]: dwp[P], dbp, loss
@@ -1812,7 +1838,13 @@ __global__ __launch_bounds__(GNT) void lyr_predict_kernel(LyrArgs a, const float
                 continue;
             }
             float dz;
-            if (a.dz_mode == NCF_DZ_BCE) {
+            if constexpr (BPR) {
+                // pairwise (BPR): a lane group walks PR_ROWS (even) consecutive rows from an
+                // even r0, so a pair never straddles a walk and the partner's z is this
+                // lane's own z[k ^ 1] -- no exchange at all.
+                static_assert(PR_ROWS % 2 == 0, "a BPR pair must not straddle a predict walk");
+                dz = bpr_dz(z[k], z[k ^ 1], rw[k], true, gl == 0, s.gb, accL);
+            } else if (a.dz_mode == NCF_DZ_BCE) {
                 const float y = (float)(uint32_t)(rw[k] >> 63);
                 dz = (sigmoidf_(z[k]) - y) / s.gb;
                 if (gl == 0) accL += bce_loss(z[k], y) / s.gb;
@@ -2165,18 +2197,22 @@ int lyr_run(const LyrArgs& a0, float* ws, int64_t R, bool train, hipStream_t st)
     float* HLp = mlp ? H[L] : nullptr;
 #define NCF_PRED(T, N) hipLaunchKernelGGL((lyr_predict_kernel<T, N>), dim3(pg), dim3(GNT), lds, st, a, HLp, \
                                           T ? Dtop : nullptr, R, G)
+#define NCF_PRED_BPR(N) hipLaunchKernelGGL((lyr_predict_kernel<true, N, true>), dim3(pg), dim3(GNT), lds, st, a, HLp, \
+                                           Dtop, R, G)
+    const bool bpr = train && a.dz_mode == NCF_DZ_BPR;  // the pairwise instantiations
     switch (NS * 2 + (train ? 1 : 0)) {
         case 2: NCF_PRED(false, 1); break;
-        case 3: NCF_PRED(true, 1); break;
+        case 3: if (bpr) NCF_PRED_BPR(1); else NCF_PRED(true, 1); break;
         case 4: NCF_PRED(false, 2); break;
-        case 5: NCF_PRED(true, 2); break;
+        case 5: if (bpr) NCF_PRED_BPR(2); else NCF_PRED(true, 2); break;
         case 6: NCF_PRED(false, 3); break;
-        case 7: NCF_PRED(true, 3); break;
+        case 7: if (bpr) NCF_PRED_BPR(3); else NCF_PRED(true, 3); break;
         case 8: NCF_PRED(false, 4); break;
-        case 9: NCF_PRED(true, 4); break;
+        case 9: if (bpr) NCF_PRED_BPR(4); else NCF_PRED(true, 4); break;
         default: return NCF_E_UNSUPPORTED;
     }
 #undef NCF_PRED
+#undef NCF_PRED_BPR
     if (!train || !mlp) return hipGetLastError() == hipSuccess ? NCF_OK : NCF_E_LAUNCH;
     float* Dcur = Da;
     float* Dnext = Db;

@@ -2121,8 +2121,13 @@ static int train_step_impl(const ncf_layout* lay, const float* params, float* gr
                            float* logits_out, void* stream) {
     if (!lay || !params || !grads || !rows || !ctl || !workspace) return NCF_E_ARG;
     if (batch_global <= 0 || world < 1 || rank < 0 || rank >= world) return NCF_E_ARG;
-    if (dz_mode != NCF_DZ_BCE && dz_mode != NCF_DZ_DLOGIT && dz_mode != NCF_DZ_KD) return NCF_E_ARG;
-    if (dz_mode != NCF_DZ_BCE && !dlogit) return NCF_E_ARG;
+    if (dz_mode != NCF_DZ_BCE && dz_mode != NCF_DZ_DLOGIT && dz_mode != NCF_DZ_KD && dz_mode != NCF_DZ_BPR)
+        return NCF_E_ARG;
+    // pairwise: rows 2k / 2k + 1 are one triple -- a rank slice (ceil(gb / world)) or an odd
+    // batch could split a pair; dlogit is ignored (labels ride in the rows, as for BCE)
+    if (dz_mode == NCF_DZ_BPR && (world != 1 || (batch_global & 1))) return NCF_E_ARG;
+    const bool has_dl = dz_mode == NCF_DZ_DLOGIT || dz_mode == NCF_DZ_KD;
+    if (has_dl && !dlogit) return NCF_E_ARG;
     const int64_t rows_max = (batch_global + world - 1) / world;
     if (workspace_bytes < ncf_workspace_bytes(lay, rows_max)) return NCF_E_ARG;
     float* slab = static_cast<float*>(workspace);
@@ -2134,7 +2139,9 @@ static int train_step_impl(const ncf_layout* lay, const float* params, float* gr
         la.params = params;
         la.grads = grads;
         la.rows = rows;
-        la.uorder = ncf_uses_user_order(lay) ? user_order : nullptr;
+        // (the pairwise kernels take rows in stream order: a pair stream is not item-grouped,
+        // and its user runs are the pairs themselves)
+        la.uorder = ncf_uses_user_order(lay) && dz_mode != NCF_DZ_BPR ? user_order : nullptr;
         la.dlogit = dlogit;
         la.ctl = ctl;
         la.batch_global = batch_global;
@@ -2154,6 +2161,14 @@ static int train_step_impl(const ncf_layout* lay, const float* params, float* gr
     const int64_t lds = train_lds_floats(e, lay, geo) * 4;
     if (lds > LDS_LIMIT_BYTES) return NCF_E_UNSUPPORTED;
     const void* fn = fact_mode(lay) ? e->train_fact[geo] : e->train[geo];
+    if (dz_mode == NCF_DZ_BPR) {  // the pairwise instantiation of the same (shape, path, geometry)
+        int nt = 0, nb = 0;
+        const KernelEntry* t0 = kernel_table(&nt);
+        const BprEntry* b = kernel_table_bpr(&nb) + (e - t0);
+        if (nb != nt || e < t0 || e >= t0 + nt) return NCF_E_UNSUPPORTED;
+        fn = fact_mode(lay) ? b->train_fact[geo] : b->train[geo];
+        if (!fn) return NCF_E_UNSUPPORTED;
+    }
     if (ensure_lds(fn, lds) != NCF_OK) return NCF_E_LAUNCH;
     TrainArgs a;
     memset(&a, 0, sizeof(a));
@@ -2162,7 +2177,7 @@ static int train_step_impl(const ncf_layout* lay, const float* params, float* gr
     a.grads = grads;
     a.rows = rows;
     // BCE mode: point dlogit at the rows so the per-row load stays unconditional
-    a.dlogit = dz_mode != NCF_DZ_BCE ? dlogit : reinterpret_cast<const float*>(rows);
+    a.dlogit = has_dl ? dlogit : reinterpret_cast<const float*>(rows);
     a.ctl = ctl;
     a.batch_global = batch_global;
     a.world = world;
@@ -2399,6 +2414,7 @@ int ncf_train_step_ais(const ncf_layout* lay, float* params, float* grads, float
     int rc = ais_args(lay, params, grads, exp_avg, exp_avg_sq, b, ranges, nranges, &x);
     if (rc != NCF_OK) return rc;
     if (!rows || !ctl || batch_global <= 0 || step_i < 0) return NCF_E_ARG;
+    // (NCF_DZ_BPR is refused here: the pairwise mode runs the two-launch step only)
     if (dz_mode != NCF_DZ_BCE && dz_mode != NCF_DZ_DLOGIT && dz_mode != NCF_DZ_KD) return NCF_E_ARG;
     if (dz_mode != NCF_DZ_BCE && !dlogit) return NCF_E_ARG;
     int geo = 0;

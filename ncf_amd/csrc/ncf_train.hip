@@ -154,7 +154,10 @@ __device__ __forceinline__ void ais_dense_block(const TrainArgs& a, int64_t n, b
     }
 }
 
-template <int F, int L, int MODE, bool FWD_ONLY, bool FACT, int NW, bool AIS = false>
+// BPR: the pairwise instantiations (NCF_DZ_BPR; built in their own translation unit,
+// ncf_train_bpr.hip) -- a template parameter, so the kernels of the other modes are the
+// same code as before the mode existed.
+template <int F, int L, int MODE, bool FWD_ONLY, bool FACT, int NW, bool AIS = false, bool BPR = false>
 __global__ __launch_bounds__(NW * WAVE, 2) void ncf_step_kernel(TrainArgs a) {
     using S_ = Shape<F, L, MODE, NW>;
     // workgroup geometry: NW waves, 16 rows each, per tile (NW = 8, or 4 for small batches)
@@ -334,6 +337,7 @@ __global__ __launch_bounds__(NW * WAVE, 2) void ncf_step_kernel(TrainArgs a) {
         base = b0 + lo;
         nloc = hi - lo;
         gb_f = (float)gb;
+        if constexpr (BPR) gb_f *= 0.5f;  // pairwise: the divisor is T = gb / 2 triples (exact)
         if (!AIS && blockIdx.x == 0 && tid == 0) {  // step snapshot for ncf_reduce_adam_step (fields no WG reads here)
             a.ctl->snap_batch = a.ctl->batch;
             a.ctl->snap_t = a.ctl->adam_t + 1;
@@ -778,7 +782,24 @@ __global__ __launch_bounds__(NW * WAVE, 2) void ncf_step_kernel(TrainArgs a) {
             // (e) loss + dlogit
             if (a.logits_out != nullptr && g == 0 && valid) a.logits_out[row0 + myq] = z;
             float dz = 0.f;
-            if (valid) {
+            if constexpr (BPR) {
+                // pairwise (BPR): rows 2k (label 1) and 2k + 1 (label 0) are one triple.
+                // Every tile height (128, 64, 32, 16 rows) and every wave's 16-row
+                // slice is even, so a pair never straddles a tile or a wave: the
+                // partner's z sits in lane l ^ 1 (row myq ^ 1, same g) -- one cross-lane
+                // exchange, no LDS round trip, no extra global load.  Both rows of a pair
+                // are valid or both are padding (stream contract); rows past nloc are
+                // published as padding.  gb_f is T = gb / 2.
+                static_assert(TRW % 2 == 0, "a BPR pair must not straddle a tile");
+                const float zo = shfl_xor(z, 1);
+                if (valid) {
+                    const bool pos = slab_[myq] != 0.f;
+                    const float d = pos ? z - zo : zo - z;  // z(2k) - z(2k+1): the same bits in both lanes
+                    const float s = (sigmoidf_(d) - 1.0f) / gb_f;
+                    dz = pos ? s : -s;
+                    if (g == 0 && pos) lossAcc += bce_loss(d, 1.0f);  // softplus(-d), once per triple
+                }
+            } else if (valid) {
                 if (a.dz_mode == NCF_DZ_BCE) {
                     const float y = slab_[myq];
                     dz = (sigmoidf_(z) - y) / gb_f;
@@ -1404,6 +1425,41 @@ __global__ __launch_bounds__(NW * WAVE, 2) void ncf_step_kernel(TrainArgs a) {
 // 16 16-byte pieces, WREG), and the per-row layer-0 wgrad gives each wave
 // CB0 = KT(0) / waves column blocks of dW0 in registers, so that kernel is built where
 // dW0 has at most 8 16x16 tiles (the factored kernel and GMF have no such term).
+#ifdef NCF_TRAIN_BPR_TU
+// The pairwise instantiations of the same (shape, geometry) set as set_geo below.
+template <int F, int L, int MODE, int G>
+static void set_geo_bpr(BprEntry& e) {
+    constexpr int NW = geo_waves(G);
+    using SG = Shape<F, L, MODE, NW>;
+    using S8 = Shape<F, L, MODE>;
+    constexpr bool regs_ok = NW == NWAVES || SG::WREG <= 16;
+#ifndef NCF_FACT_WREG_MAX
+#define NCF_FACT_WREG_MAX 16
+#endif
+    constexpr bool fregs_ok = NW == NWAVES || SG::WREG <= NCF_FACT_WREG_MAX;
+    if constexpr (regs_ok && (!S8::MLP || S8::MT(0) * S8::KT(0) <= 8 || NW == NWAVES))
+        e.train[G] = reinterpret_cast<const void*>(&ncf_step_kernel<F, L, MODE, false, false, NW, false, true>);
+    else
+        e.train[G] = nullptr;
+    if constexpr (S8::MLP && fregs_ok)
+        e.train_fact[G] = reinterpret_cast<const void*>(&ncf_step_kernel<F, L, MODE, false, true, NW, false, true>);
+    else
+        e.train_fact[G] = nullptr;
+}
+template <int F, int L, int MODE>
+static BprEntry make_entry() {
+    BprEntry e;
+    set_geo_bpr<F, L, MODE, GEO_8>(e);
+    set_geo_bpr<F, L, MODE, GEO_4>(e);
+    set_geo_bpr<F, L, MODE, GEO_2>(e);
+    set_geo_bpr<F, L, MODE, GEO_1>(e);
+    return e;
+}
+#define NCF_TABLE_ENTRY BprEntry
+#define NCF_TABLE_FN kernel_table_bpr
+#else
+#define NCF_TABLE_ENTRY KernelEntry
+#define NCF_TABLE_FN kernel_table
 template <int F, int L, int MODE, int G>
 static void set_geo(KernelEntry& e) {
     constexpr int NW = geo_waves(G);
@@ -1446,9 +1502,11 @@ static KernelEntry make_entry() {
     e.w_total = S_::W_TOTAL;
     return e;
 }
+#endif
 
-const KernelEntry* kernel_table(int* n) {
-    static const KernelEntry table[] = {
+// (one list for both tables: kernel_table_bpr()[k] is the pairwise form of kernel_table()[k])
+const NCF_TABLE_ENTRY* NCF_TABLE_FN(int* n) {
+    static const NCF_TABLE_ENTRY table[] = {
 #ifdef NCF_DEV_ONE
         make_entry<16, 3, NCF_MODEL_NEUMF>(),
 #else

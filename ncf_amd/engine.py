@@ -152,10 +152,23 @@ class TrainEngine:
             self._drop_graphs()
 
     def __init__(self, model, lr=1e-3, optimizer="adam", betas=(0.9, 0.999), eps=1e-8,
-                 world_size=1, rank=0, process_group=None, max_batches=1 << 16, dp_mode=None, distill=None):
+                 world_size=1, rank=0, process_group=None, max_batches=1 << 16, dp_mode=None, distill=None,
+                 loss="bce"):
         """distill: an ``ncf_amd.distill.DeviceDistillPlan`` -- the student step then
         runs ncf_train_step_kd (teacher logits of the epoch stream computed once per
-        epoch by ncf_forward) plus ncf_kd_feature_step for the feature terms."""
+        epoch by ncf_forward) plus ncf_kd_feature_step for the feature terms.
+        loss: "bce" (the reference's BCEWithLogitsLoss, train_neumf.py:86) or "bpr" --
+        the pairwise ranking loss over a pair stream (ops.build_pair_stream: rows 2k /
+        2k + 1 are (u, i+) / (u, i-)); the step launches NCF_DZ_BPR, batch_size counts
+        rows (two per triple).  Single process, no distillation."""
+        if loss not in ("bce", "bpr"):
+            raise ValueError(f"loss {loss!r}")
+        if loss == "bpr" and int(world_size) > 1:
+            raise ValueError("loss 'bpr' is single-process: a rank slice of a batch could split a pair")
+        if loss == "bpr" and distill is not None:
+            raise ValueError("loss 'bpr' does not combine with distillation")
+        self.loss = loss
+        self._dz = L.DZ_BPR if loss == "bpr" else L.DZ_BCE
         self.model = model
         self.distill = distill
         if process_group is None and int(world_size) > 1:
@@ -280,8 +293,11 @@ class TrainEngine:
         (`checked`, e.g. Trainer on the host arrays)."""
         if rows.dtype != torch.int64 or not rows.is_contiguous() or rows.device != self.device:
             raise ValueError("epoch stream: contiguous int64 packed rows on the engine's device")
+        if self.loss == "bpr" and (int(batch_size) % 2 or rows.numel() % 2):
+            raise ValueError("loss 'bpr': the stream and every batch hold whole pairs (even row counts)")
         if not checked:
-            ops.check_rows(rows, self.model.user_num, self.model.item_num)
+            (ops.check_pair_rows if self.loss == "bpr" else ops.check_rows)(rows, self.model.user_num,
+                                                                             self.model.item_num)
         n = rows.numel()
         self.rows = rows
         self.n_total = n
@@ -777,8 +793,8 @@ class TrainEngine:
         small-batch kernel with per-row layer 0; response distillation only (its logits
         ride in the launch, feature terms would add into the gradient separately)."""
         mode = {True: "1", False: "0"}.get(self.ADAM_IN_STEP, self.ADAM_IN_STEP)
-        if mode == "0" or not self._fused_optimizer or self.lazy:
-            return False
+        if mode == "0" or not self._fused_optimizer or self.lazy or self.loss == "bpr":
+            return False  # (ncf_train_step_ais refuses the pairwise mode)
         if self.distill is not None and self.distill.keys:
             return False
         if not L.hip().ncf_ais_supported(ctypes.byref(self.lay)):
@@ -840,7 +856,7 @@ class TrainEngine:
         L.check(L.hip().ncf_train_step(ctypes.byref(self.lay), self.flat.data_ptr(), self.grads.data_ptr(),
                                        self.rows.data_ptr(), self.user_order_ptr(), None, self.ctl.data_ptr(),
                                        self.batch_size,
-                                       self.world_size, self.rank, L.DZ_BCE, self.ws.data_ptr(),
+                                       self.world_size, self.rank, self._dz, self.ws.data_ptr(),
                                        self.ws.numel() * 4, None, st), "ncf_train_step")
 
     def _reduce_adam(self):
@@ -934,7 +950,7 @@ class TrainEngine:
                 return
             L.check(lib.ncf_train_step(lay, self.flat.data_ptr(), self.grads.data_ptr(), self.rows.data_ptr(),
                                        self.user_order_ptr(), None, self.ctl.data_ptr(), self.batch_size, self.world_size, self.rank,
-                                       L.DZ_BCE, self.ws.data_ptr(), self.ws.numel() * 4, None, sp), "ncf_train_step")
+                                       self._dz, self.ws.data_ptr(), self.ws.numel() * 4, None, sp), "ncf_train_step")
         launch()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(st)
@@ -1143,7 +1159,7 @@ class TrainEngine:
             (g_uc if s + 1 < n else g_u).replay()
 
     def epoch_losses(self):
-        """Per-batch mean BCE of the last epoch (host copy).  zero1: the rank owning
+        """Per-batch mean loss (BCE, or BPR per triple) of the last epoch (host copy).  zero1: the rank owning
         the loss slot recorded it; it is broadcast to the others (a collective: every
         rank calls this)."""
         if self.dp_mode == "zero1":

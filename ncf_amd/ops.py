@@ -147,6 +147,79 @@ def pack_rows_host(users, items, labels=None):
     return r
 
 
+# ---------------------------------------------------------------------------
+# Pairwise (BPR) training stream (include/ncf_hip.h NCF_DZ_BPR, ncf_build_pair_stream)
+def bpr_stream_host(pos_users, pos_items, neg, num_ng, perm=None):
+    """The pair stream of ncf_build_pair_stream in NumPy (int64 packed rows, length
+    2 * S, S = len(pos_users) * num_ng): triple k is t = perm[k] (identity when None),
+    positive p = t // num_ng -- row 2k (pos_users[p], pos_items[p], label 1), row 2k + 1
+    (pos_users[p], neg[t], label 0)."""
+    pu = np.asarray(pos_users).astype(np.int64).reshape(-1)
+    pi = np.asarray(pos_items).astype(np.int64).reshape(-1)
+    ng = int(num_ng)
+    S = pu.size * ng
+    neg = np.asarray(neg).astype(np.int64).reshape(-1)
+    if pu.size != pi.size or ng < 0 or neg.size < S:
+        raise ValueError("bpr_stream_host: one item per positive and num_ng negatives per positive")
+    t = np.arange(S, dtype=np.int64) if perm is None else np.asarray(perm).astype(np.int64).reshape(-1)
+    if t.size != S:
+        raise ValueError("bpr_stream_host: perm must order the n_pos * num_ng triples")
+    p = t // max(ng, 1)
+    out = np.empty(2 * S, dtype=np.int64)
+    out[0::2] = pack_rows_host(pu[p], pi[p], np.ones(S, dtype=np.int64))
+    out[1::2] = pack_rows_host(pu[p], neg[t])
+    return out
+
+
+def build_pair_stream(pos_users_i32, pos_items_i32, neg_i32, num_ng, perm=None, out=None):
+    """ncf_build_pair_stream on the current stream: int32 device tensors of the positives
+    and their negatives (ncf_build_rows' layout), perm an int64 device permutation of the
+    S = n_pos * num_ng triples (None: identity) -> 2 * S packed int64 rows."""
+    dev = pos_users_i32.device
+    P, ng = pos_users_i32.numel(), int(num_ng)
+    S = P * ng
+    for t, what in ((pos_users_i32, "pos_users"), (pos_items_i32, "pos_items"), (neg_i32, "neg")):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"build_pair_stream: {what} must be a contiguous int32 tensor on one device")
+    if pos_items_i32.numel() != P or ng < 0 or (S > 0 and (neg_i32 is None or neg_i32.numel() < S)):
+        raise ValueError("build_pair_stream: one item per positive and num_ng negatives per positive")
+    if perm is not None and (perm.dtype != torch.int64 or perm.numel() != S or not perm.is_contiguous()
+                             or perm.device != dev):
+        raise ValueError("build_pair_stream: perm must be a contiguous int64 permutation of the triples")
+    if out is None:
+        out = torch.empty(2 * S, dtype=torch.int64, device=dev)
+    elif out.numel() != 2 * S or out.dtype != torch.int64 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("build_pair_stream out: 2 * n_pos * num_ng contiguous int64")
+    L.check(L.hip().ncf_build_pair_stream(pos_users_i32.data_ptr(), pos_items_i32.data_ptr(), P,
+                                          neg_i32.data_ptr() if S else None, ng,
+                                          None if perm is None else perm.data_ptr(), out.data_ptr(),
+                                          L.stream_ptr(dev)), "ncf_build_pair_stream")
+    return out
+
+
+def check_pair_rows(rows, user_num, item_num):
+    """check_rows for a pair stream (NCF_DZ_BPR): also ValueError for an odd length, a
+    pair whose labels are not (1, 0) or whose users differ (padding pairs: both rows
+    with user -1).  `rows`: packed int64, a device tensor or a host array."""
+    if not isinstance(rows, torch.Tensor):
+        rows = torch.from_numpy(np.ascontiguousarray(np.asarray(rows), dtype=np.int64))
+    n = rows.numel()
+    if n % 2:
+        raise ValueError("pair stream: an odd number of rows")
+    if n == 0:
+        return
+    a, b = rows[0::2], rows[1::2]
+    ua, ub = a & 0xFFFFFFFF, b & 0xFFFFFFFF
+    pad = ua == 0xFFFFFFFF
+    bad_y = (((a >> 63) & 1) != 1) | (((b >> 63) & 1) != 0)
+    flags = torch.stack([(bad_y & ~pad).any(), (ua != ub).any()]).tolist()
+    if flags[1]:
+        raise ValueError("pair stream: the two rows of a pair have different users")
+    if flags[0]:
+        raise ValueError("pair stream: the labels of a pair are not (1, 0)")
+    check_rows(rows, user_num, item_num)
+
+
 def default_canonical():
     """True when torch.distributed runs more than one rank (the grouping must then be
     NCF_PREP_CANONICAL so every rank's stream is identical)."""

@@ -24,6 +24,9 @@ the state restored) and its permutation words generated on a second thread; its
 rows, permutation and grouping by item are then built on a side stream, under
 epoch e's steps, into the other of two output buffers (the step graphs are
 captured once per buffer), so the epoch boundary is one stream wait.
+EpochPipeline(pairwise=True) builds the pair stream of the BPR mode instead: the same
+sampler call and torch draws, ncf_randperm over the P * num_ng (user, item+, item-)
+triples and ncf_build_pair_stream (two rows per triple, no grouping).
 When epoch e+1 starts, the real draws are made and compared with what was used;
 a mismatch (someone else consumed either generator in between) discards the
 prefetch, and the epoch is built synchronously.
@@ -113,11 +116,16 @@ class EpochPipeline:
     depth + 1 sets of buffers, one being trained from."""
 
     def __init__(self, dataset, device, batch_size, item_num, user_num=None, prefetch=True, depth=None,
-                 canonical=None):
+                 canonical=None, pairwise=False):
         """canonical: rows of one item inside a batch in (user, label) order
         (ncf_prepare_epoch2 NCF_PREP_CANONICAL) -- every rank of a data-parallel group
         then builds the identical stream; None: on when torch.distributed runs more
-        than one rank (ops.default_canonical)."""
+        than one rank (ops.default_canonical).
+        pairwise: the epoch is the pair stream of the BPR mode (NCF_DZ_BPR) -- the same
+        sampler call and the DataLoader's same two torch draws, then a
+        DataLoader(shuffle=True) order over the S = P * num_ng (user, item+, item-)
+        triples: ncf_randperm over S and ncf_build_pair_stream into the slot's 2 S-row
+        output.  No item grouping; batch_size is unused."""
         self.ds = dataset
         self.device = torch.device(device)
         self.batch_size = int(batch_size)
@@ -136,19 +144,24 @@ class EpochPipeline:
         self.pu = torch.as_tensor(pu, dtype=torch.int32).to(dev)
         self.pi = torch.as_tensor(pi, dtype=torch.int32).to(dev)
         self.S = self.P * self.ng
-        self.n = self.P + self.S
+        self.pairwise = bool(pairwise)
+        if self.pairwise and self.ng == 0:
+            raise ValueError("pairwise epochs need sampled negatives (num_ng > 0)")
+        # n: entries the epoch's permutation orders (rows, or triples); n_out: rows of the stream
+        self.n = self.S if self.pairwise else self.P + self.S
+        self.n_out = 2 * self.S if self.pairwise else self.n
         if depth is None:
             depth = int(os.environ.get("NCF_PIPE_DEPTH", "2"))
         self.depth = max(1, int(depth)) if prefetch else 0
         self.prefetch = prefetch
         K = self.depth + 1
         # shared by the builds (issued in epoch order on one stream)
-        self.rows = torch.empty(self.n, dtype=torch.int64, device=dev)
+        self.rows = None if self.pairwise else torch.empty(self.n, dtype=torch.int64, device=dev)
         self.perm = torch.empty(self.n, dtype=torch.int64, device=dev)
         self.fy_ws = torch.empty(int(L.hip().ncf_randperm_workspace(self.n)), dtype=torch.uint8, device=dev)
         self.prep = ops.EpochPrep(dev, canonical=canonical)
         # per slot
-        self._out = [torch.empty(self.n, dtype=torch.int64, device=dev) for _ in range(K)]
+        self._out = [torch.empty(self.n_out, dtype=torch.int64, device=dev) for _ in range(K)]
         self._neg_host = [torch.empty(max(1, self.S), dtype=torch.int32).pin_memory() for _ in range(K)]
         self._words_host = [torch.empty(max(1, self.n - 1), dtype=torch.int32).pin_memory() for _ in range(K)]
         self._neg_dev = [torch.empty(max(1, self.S), dtype=torch.int32, device=dev) for _ in range(K)]
@@ -223,15 +236,21 @@ class EpochPipeline:
             stream.wait_event(self._free[slot])
         staged.t0 = torch.cuda.Event(enable_timing=True)
         staged.t0.record(stream)
-        L.check(lib.ncf_build_rows(self.pu.data_ptr(), self.pi.data_ptr(), self.P,
-                                   self._neg_dev[slot].data_ptr() if self.S else None, self.ng,
-                                   self.rows.data_ptr(), st), "ncf_build_rows")
+        if not self.pairwise:
+            L.check(lib.ncf_build_rows(self.pu.data_ptr(), self.pi.data_ptr(), self.P,
+                                       self._neg_dev[slot].data_ptr() if self.S else None, self.ng,
+                                       self.rows.data_ptr(), st), "ncf_build_rows")
         L.check(lib.ncf_randperm(self._words_dev[slot].data_ptr(), self.n, self.perm.data_ptr(),
                                  self.fy_ws.data_ptr(), self.fy_ws.numel(), st), "ncf_randperm")
         staged.built = torch.cuda.Event(enable_timing=True)
         staged.built.record(stream)
-        with torch.cuda.stream(stream):
-            self.prep(self.rows, self.perm, self.batch_size, self.item_num, out=self._out[slot])
+        if self.pairwise:  # the triples in permutation order, two rows each (no grouping)
+            L.check(lib.ncf_build_pair_stream(self.pu.data_ptr(), self.pi.data_ptr(), self.P,
+                                              self._neg_dev[slot].data_ptr(), self.ng, self.perm.data_ptr(),
+                                              self._out[slot].data_ptr(), st), "ncf_build_pair_stream")
+        else:
+            with torch.cuda.stream(stream):
+                self.prep(self.rows, self.perm, self.batch_size, self.item_num, out=self._out[slot])
         staged.ready = torch.cuda.Event(enable_timing=True)
         staged.ready.record(stream)
         hook = self.on_built

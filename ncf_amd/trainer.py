@@ -33,12 +33,29 @@ from .engine import TrainEngine
 from .metrics import evaluate_rows_device
 
 
+def bpr_host_epoch(ds):
+    """One pairwise (BPR) epoch built on the host (the NCF_HOST_EPOCH=1 path of
+    Trainer(loss="bpr")): the reference's ng_sample() (NumPy global stream), the
+    DataLoader(shuffle=True) protocol's two torch draws and a randperm over the
+    S = P * num_ng triples (data.epoch_permutation), packed by ops.bpr_stream_host.
+    Returns the 2 S packed rows (int64 numpy)."""
+    ds.ng_sample()
+    _, items, _ = ds.arrays()
+    P, ng = len(ds._ps_u), int(ds.num_ng)
+    perm = epoch_permutation(P * ng).numpy()
+    return ops.bpr_stream_host(ds._ps_u, ds._ps_i, items[P:], ng, perm)
+
+
 class Trainer:
     def __init__(self, model, train_dataset: NCFData, test_loader=None, *, batch_size=256, lr=1e-3,
                  optimizer="adam", top_k=10, device=None, world_size=1, rank=0, process_group=None,
-                 use_graph=True, save_path=None, verbose=True, test_batch=None, distill=None):
+                 use_graph=True, save_path=None, verbose=True, test_batch=None, distill=None, loss="bce"):
         """distill: a distillation module (ncf_amd.distill) whose student is `model`:
-        every step then trains the student on that module's loss (device plan)."""
+        every step then trains the student on that module's loss (device plan).
+        loss: "bce" (the reference loop) or "bpr" -- the pairwise ranking loss: an epoch
+        is a DataLoader(shuffle=True) pass over the P * num_ng (user, item+, item-)
+        triples of ng_sample(), batch_size counts triples (the engine gets
+        2 * batch_size rows per batch) and Loss= is the mean BPR loss per triple."""
         self.model = model
         self.ds = train_dataset
         self.test_loader = test_loader
@@ -52,9 +69,16 @@ class Trainer:
         self.world_size, self.rank = int(world_size), int(rank)
         if distill is not None and distill.student_model is not model:
             raise ValueError("distill.student_model must be the model being trained")
+        if loss not in ("bce", "bpr"):
+            raise ValueError(f"loss {loss!r}")
+        if loss == "bpr" and int(train_dataset.num_ng) == 0:
+            raise ValueError("loss 'bpr' needs sampled negatives (num_ng > 0)")
+        self.loss = loss
+        # rows per engine batch: a BPR batch of batch_size triples is 2 * batch_size rows
+        self._batch_rows = 2 * self.batch_size if loss == "bpr" else self.batch_size
         plan = distill.device_plan() if distill is not None else None
         self.engine = TrainEngine(model, lr=lr, optimizer=optimizer, world_size=world_size, rank=rank,
-                                  process_group=process_group, distill=plan)
+                                  process_group=process_group, distill=plan, loss=loss)
         self.use_graph = use_graph
         self.save_path = save_path
         self.verbose = verbose and self.rank == 0
@@ -74,12 +98,21 @@ class Trainer:
             if self._pipe is None:
                 from .pipeline import EpochPipeline
                 self._pipe = EpochPipeline(self.ds, self.device, self.batch_size, int(self.model.item_num),
-                                           user_num=int(self.model.user_num), canonical=self.world_size > 1)
+                                           user_num=int(self.model.user_num), canonical=self.world_size > 1,
+                                           pairwise=self.loss == "bpr")
                 self.engine.stream_buffers = self._pipe.buffers  # step graphs captured for both
                 self._pipe.on_built = self.engine.owner_prebuild  # dp_mode "owner": lists built with each epoch
             # fit() evaluates after every epoch (one torch draw): the next epoch's
             # sampler seed is peeked past it
             return self._pipe.next_epoch(peek_eval_draw=True)
+        if self.loss == "bpr":
+            pairs = bpr_host_epoch(self.ds)
+            u, i, _ = self.ds.arrays()
+            ops.check_ids(u, i, int(self.model.user_num), int(self.model.item_num))
+            if getattr(self, "_rows", None) is None or self._rows.numel() != pairs.size:
+                self._rows = torch.empty(pairs.size, dtype=torch.int64, device=self.device)
+            self._rows.copy_(torch.from_numpy(pairs))
+            return self._rows
         self.ds.ng_sample()
         u, i, y = self.ds.arrays()
         n = len(u)
@@ -158,7 +191,7 @@ class Trainer:
 
     def train_epoch(self):
         rows = self._epoch_stream()
-        self.engine.set_epoch_stream(rows, self.batch_size, checked=True)  # ids checked on the host
+        self.engine.set_epoch_stream(rows, self._batch_rows, checked=True)  # ids checked on the host
         self.engine.run(self.engine.num_batches, use_graph=self.use_graph)
         return float(np.mean(self.engine.epoch_losses()))
 
@@ -227,7 +260,7 @@ class Trainer:
                 ev0 = torch.cuda.Event(enable_timing=True)
                 ev0.record()
                 rows = self._epoch_stream()
-                self.engine.set_epoch_stream(rows, self.batch_size, checked=True)
+                self.engine.set_epoch_stream(rows, self._batch_rows, checked=True)
                 self.engine.run(self.engine.num_batches, use_graph=self.use_graph)
                 self.model.eval()
                 nb = self.engine.num_batches

@@ -64,10 +64,12 @@ def train_neumf(args, device):
     print(f"Model parameters: {param_count:,}")
     opt, lr = ("sgd", args.lr * 10) if args.pretraining else ("adam", args.lr)
     trainer = Trainer(model, train_dataset, test_loader, batch_size=args.batch_size, lr=lr, optimizer=opt,
-                      top_k=args.top_k, device=device)
+                      top_k=args.top_k, device=device, loss=args.loss)
     print(f"Training for {args.epochs} epochs...")
     suffix = "pre" if args.pretraining else "end"
-    fname = f"NeuMF_{suffix}_{args.num_layers}l_{args.factor_num}f_best.pth"
+    # a pairwise (BPR) run never overwrites a BCE checkpoint: "_bpr" before "_best.pth"
+    tag = "_bpr" if args.loss == "bpr" else ""
+    fname = f"NeuMF_{suffix}_{args.num_layers}l_{args.factor_num}f{tag}_best.pth"
 
     def save(m):
         if args.save:
@@ -103,6 +105,9 @@ def main():
     p.add_argument("--top_k", type=int, default=config.top_k)
     p.add_argument("--save", action="store_true", default=True)
     p.add_argument("--gpu", type=str, default="0")
+    p.add_argument("--loss", type=str, default="bce", choices=["bce", "bpr"],
+                   help="bce: the reference objective; bpr: pairwise ranking loss over (user, item+, item-) "
+                        "triples (batch_size then counts triples)")
     p.add_argument("--seed", type=int, default=None, help="seed numpy + torch (the reference never seeds)")
     args = p.parse_args()
     if args.seed is not None:

@@ -14,7 +14,7 @@ contiguous shard of each global batch.  The gradient exchange forms
 * ``"allreduce"``: one all-reduce of the flat gradient bucket, replicated Adam.
 * ``"owner"``: embedding row id owned by rank id % W; the touched rows' gradients go
   to their owners and the rows each rank's next batch reads come back, two
-  fixed-size all-to-alls per step (device kernels ncf_owner_*, engine.py);
+  fixed-size all-to-alls per step (device kernels ncf_owner_*, exchange.py);
   ``owner_gather_rows`` brings every replica up to date at the end of a run.
 
 All keep dense-Adam parity with the single-device run (Adam is elementwise).
@@ -104,12 +104,12 @@ def _coll_ok(t, group):
     return dist.get_backend(group) != "gloo" or t.device.type == "cpu"
 
 
-def _all_reduce(t, group):
+def _all_reduce(t, group, op=dist.ReduceOp.SUM):
     if _coll_ok(t, group):
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(t, op=op, group=group)
         return t
     h = t.cpu()
-    dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
+    dist.all_reduce(h, op=op, group=group)
     t.copy_(h)
     return t
 

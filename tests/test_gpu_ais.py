@@ -40,7 +40,7 @@ def _run(on, U, I, f, nl, mt, B, T, graph=True, chunks=1, seed=0):
         torch.cuda.synchronize()
         ctl = eng.ctl.cpu().numpy()
         assert int(ctl[0]) == T and int(ctl[1]) == T, ctl  # batch, adam_t
-        assert not getattr(eng, "_ais_live", False)
+        assert not eng._ais_live
         return ({k: v.detach().cpu().numpy().copy() for k, v in m.state_dict().items()},
                 eng.epoch_losses()[:T].copy(), (u, i, y),
                 (eng.exp_avg.cpu().numpy().copy(), eng.exp_avg_sq.cpu().numpy().copy()))

@@ -53,19 +53,19 @@ def _run(world, rank, group, mt, f, nl, use_graph, dp_mode=None):
         # every shard range cut in two (the same elements): a table window no longer
         # sits inside one range, so ncf_adam_step_fact takes its two-launch form
         import ctypes
-        rng = [(eng._sranges[2 * k], eng._sranges[2 * k + 1]) for k in range(eng._nsranges)]
+        rng = [(eng.exchange._sranges[2 * k], eng.exchange._sranges[2 * k + 1]) for k in range(eng.exchange._nsranges)]
         cut = []
         for b, e in rng:
             mid = b + ((e - b) // 2 // 64) * 64
             cut += [(b, mid), (mid, e)] if b < mid < e else [(b, e)]
         assert len(cut) > len(rng)
-        eng._sranges = (ctypes.c_int64 * (2 * len(cut)))(*[x for q in cut for x in q])
-        eng._nsranges = len(cut)
+        eng.exchange._sranges = (ctypes.c_int64 * (2 * len(cut)))(*[x for q in cut for x in q])
+        eng.exchange._nsranges = len(cut)
     u, i, y = _batches()
     rows = torch.as_tensor(ops.pack_rows_host(u, i, y), device="cuda:0")
     eng.set_epoch_stream(rows, B)
     if split:
-        assert eng._fact_shard  # the factored shard expansion is what the split ranges exercise
+        assert eng.exchange.fact_shard  # the factored shard expansion is what the split ranges exercise
     eng.run(T, use_graph=use_graph)
     torch.cuda.synchronize()
     if want is not None:

@@ -87,7 +87,7 @@ def _c3_run(world, rank, group, batch=B):
     eng = tr.engine
     losses = eng.epoch_losses()[:eng.num_batches].astype(np.float64).copy()
     if eng.dp_mode == "zero1":
-        assert eng._fact_shard  # the sharded factored expansion ran
+        assert eng.exchange.fact_shard  # the sharded factored expansion ran
     return _flat(model), losses, eng.dp_mode
 
 

@@ -132,7 +132,7 @@ struct TrainArgs {
     unsigned long long* stamps;  // diagnostics: per-workgroup s_memtime stamps (nullptr in production)
     // NCF_LAYOUT_USER_STORE: the user-side embedding gradients of row k of the slice go
     // with plain stores to ustore[k * uw ...] ([Um part DM][Ug part F]) instead of float
-    // atomics into grads; user_sum_kernel (ncf_ops.hip) sums them per user afterwards.
+    // atomics into grads; user_sum_kernel (ncf_step.hip) sums them per user afterwards.
     float* ustore;
     int uw;
     AisArgs ais;  // ncf_step_kernel<..., AIS = true> only

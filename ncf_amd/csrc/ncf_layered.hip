@@ -13,14 +13,14 @@
 //   lyr_bwd_data<FIRST>   dY_{k-1} = (dY_k W_k) * [H_k > 0], or for k = 0 the
 //                         Um/Im embedding scatter-add
 //
-// Factored layer 0 (train, tables of at most FACT_MAX_ROWS rows, ncf_ops.hip
+// Factored layer 0 (train, tables of at most FACT_MAX_ROWS rows, ncf_step.hip
 // fact_mode): with W0 = [W0u | W0i] the layer-0 pre-activation of a row is
 // Um[u] W0u^T + Im[i] W0i^T, so
 //   lyr_proj              P = [Um W0u^T ; Im W0i^T]     (U + I rows, once per step)
 //   lyr_fwd0_fact         H_1 = ReLU(P[u] + P[U + i] + b_0)   (a gather per row)
 //   lyr_scatter0          dY_0 rows scatter-added into the user / item rows of the
 //                         gradient buffer (item runs summed first), db_0
-// and fact_expand_kernel (ncf_ops.hip) turns those per-row-sum rows into dUm, dIm
+// and fact_expand_kernel (ncf_fact.hip) turns those per-row-sum rows into dUm, dIm
 // and the dW0 partials -- three (U + I)-row GEMMs in place of three B-row ones.
 //
 // All three GEMM shapes run on one MFMA core: v_mfma_f32_16x16x4f32 (exact
@@ -2043,7 +2043,7 @@ int lyr_run(const LyrArgs& a0, float* ws, int64_t R, bool train, hipStream_t st)
     const bool vec = (F % 4) == 0;  // every tower width a multiple of 4: 16-byte operand loads
     float* Pj = nullptr;  // factored layer 0: table projections
     if (fact) {
-        off += rup64(a.fact_part_floats);  // dW0 partials (ncf_ops.hip fact_partials)
+        off += rup64(a.fact_part_floats);  // dW0 partials (ncf_step.hip fact_partials)
         Pj = ws + off;
         off += rup64(((int64_t)lay.user_num + lay.item_num) * DM);
     }

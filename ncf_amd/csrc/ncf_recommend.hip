@@ -1,4 +1,5 @@
-// Full-catalogue top-K recommendation (ncf_recommend, include/ncf_hip.h; since ABI 20).
+// Evaluation kernels.  HR / NDCG per batch of scored candidates (ncf_hr_ndcg), and the
+// full-catalogue top-K recommendation (ncf_recommend, include/ncf_hip.h; since ABI 20):
 //
 // Fused path (every shape with a fused kernel: dm <= 64).  Layer 0 factors per entity,
 //   pre0(u, i) = Pu[u] + Pi[i],  Pu = Um W0[:, :dm]^T,  Pi = Im W0[:, dm:]^T + b0,
@@ -579,6 +580,48 @@ static int rc_ensure_lds(const void* fn, int64_t bytes) {
 
 static int rc_status() { return hipGetLastError() == hipSuccess ? NCF_OK : NCF_E_LAUNCH; }
 
+// ---------------------------------------------------------------------------
+// HR / NDCG per batch.  One wave per batch; the batch's logits staged in LDS.
+// rank(e) = #{e' : x[e'] > x[e] or (x[e'] == x[e] and e' < e)}  (stable order)
+constexpr int HR_MAXB = 1024;
+__global__ __launch_bounds__(256) void hr_ndcg_kernel(const float* __restrict__ logits, const int32_t* __restrict__ items,
+                                                      int64_t n, int bs, int k, int64_t nb, int32_t* hr, float* ndcg) {
+    __shared__ float sx[4][HR_MAXB];
+    __shared__ int si[4][HR_MAXB];
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * 4 + w;
+    if (b >= nb) return;  // wave-uniform; no workgroup barrier below
+    const int64_t r0 = b * bs;
+    const int cnt = (int)((n - r0) < bs ? (n - r0) : bs);
+    for (int e = l; e < cnt; e += 64) {
+        sx[w][e] = logits[r0 + e];
+        si[w][e] = items[r0 + e];
+    }
+    __builtin_amdgcn_wave_barrier();  // LDS is in-order per wave: the writes above are seen below
+    const int gt = si[w][0];
+    int best = 0x7fffffff;
+    for (int e = l; e < cnt; e += 64) {
+        if (si[w][e] != gt) continue;
+        const float x = sx[w][e];
+        int rank = 0;
+        for (int e2 = 0; e2 < cnt; ++e2) {
+            const float y = sx[w][e2];
+            rank += (y > x) || (y == x && e2 < e);
+        }
+        if (rank < k && rank < best) best = rank;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const int o = __shfl_xor(best, m, 64);
+        best = o < best ? o : best;
+    }
+    if (l == 0) {
+        const bool hit = best < k;
+        hr[b] = hit ? 1 : 0;
+        ndcg[b] = hit ? (float)(1.0 / log2((double)best + 2.0)) : 0.0f;
+    }
+}
+
 }  // namespace ncf
 
 using namespace ncf;
@@ -667,6 +710,18 @@ int ncf_recommend(const ncf_layout* lay, const float* params, const int32_t* use
                            (size_t)RC_WAVES * (2 * K + 64) * 4, st, logits, users, qb, uc, I, K, seen_ptr, seen_items,
                            items_out, scores_out);
     }
+    return rc_status();
+}
+
+int ncf_hr_ndcg(const float* logits, const int32_t* items, int64_t n, int batch, int top_k, int32_t* hr, float* ndcg,
+                void* stream) {
+    if (!logits || !items || !hr || !ndcg || n <= 0 || batch <= 0 || batch > HR_MAXB || top_k <= 0) return NCF_E_ARG;
+    const int64_t nb = (n + batch - 1) / batch;
+    const int64_t last = n - (nb - 1) * batch;
+    if (top_k > batch || top_k > last) return NCF_E_ARG;  // torch.topk: "selected index k out of range"
+    const int64_t grid = (nb + 3) / 4;
+    hipLaunchKernelGGL(hr_ndcg_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, logits, items, n, batch,
+                       top_k, nb, hr, ndcg);
     return rc_status();
 }
 

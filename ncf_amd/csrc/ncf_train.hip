@@ -85,7 +85,7 @@ __device__ __forceinline__ void set_r(f4& v, int r, float x) {
 //   dUm[u] = (sum over the batch rows r of user u of D0_r) W0u,   dW0u = sum_u G_u^T Um[u]
 // (G_u = that row sum), likewise for items: the step scatter-adds D0_r (width
 // S(1) = DM) into the user and item rows of the gradient buffer and
-// fact_expand_kernel (ncf_ops.hip) turns those sums into dUm, dIm, dW0 with
+// fact_expand_kernel (ncf_fact.hip) turns those sums into dUm, dIm, dW0 with
 // (U + I) / 16 tile GEMMs instead of B / 16.  Every wave then touches only its own
 // rows of LDS after the weight prologue, so tiles need no workgroup barrier.
 // NCF_LAYOUT_ADAM_IN_STEP, workgroups [ntrain, grid) of a training launch: update n

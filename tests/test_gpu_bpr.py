@@ -3,7 +3,7 @@ kernel that forms dz, TrainEngine(loss="bpr"), EpochPipeline(pairwise=True) and
 Trainer(loss="bpr"), against the CPU oracle (tests/bpr_checks.py: OracleNCF under torch
 autograd with ncf_amd.losses.bpr_loss and torch.optim) at the project's tolerances.
 
-Which shapes reach which dz site (ncf_ops.hip train_step_impl, ncf_layered.hip lyr_run):
+Which shapes reach which dz site (ncf_step.hip train_step_impl, ncf_layered.hip lyr_run):
   * ncf_train.hip ncf_step_kernel<..., BPR> (fused path, ncf_supported == 1): NeuMF(8,3),
     NeuMF(16,3), MLP(16,2), GMF(16,1).  Untuned layouts run the 8-wave kernel (128-row
     tiles), factored layer 0 for the tower shapes (U + I <= 32,768); ncf_layout_tune at

@@ -189,7 +189,7 @@ def test_lazy_adam_bitwise_equals_dense_over_two_epochs():
 
 def test_step_scalar_cache_follows_its_inputs():
     """The optimizer launches take step t's (-lr/bc1, sqrt(bc2)) from a per-control-
-    block cache that step t - 1's launch filled (ncf_ops.hip ScCache).  Steps out of
+    block cache that step t - 1's launch filled (ncf_adam.h ScCache).  Steps out of
     order, repeated, and with lr / beta changes between them must give bitwise what a
     fresh control block (no usable entry: the double pows) gives."""
     import ncf_amd._lib as L

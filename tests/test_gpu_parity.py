@@ -309,7 +309,7 @@ def test_one_step_c4_id_space_per_row_layer0(mt, B):
 
 @pytest.mark.parametrize("U,I,fact", [(16384, 16384, True), (16384, 16385, False)])
 def test_one_step_fact_boundary(U, I, fact):
-    """Both sides of fact_mode (U + I <= 32768, ncf_ops.hip): the factored and the
+    """Both sides of fact_mode (U + I <= 32768, ncf_step.hip): the factored and the
     per-row layer-0 kernels give the same gradients."""
     lay = _one_step("NeuMF-end", 16, 3, 8192, U, I, seed=14)
     assert _fact_mode(lay) == fact

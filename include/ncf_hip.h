@@ -22,6 +22,8 @@ extern "C" {
 #endif
 
 /* 21: pairwise (BPR) training: NCF_DZ_BPR of ncf_train_step, ncf_build_pair_stream.
+ * Added within 21 (purely additive, the version is unchanged; probe with dlsym):
+ * ncf_neighbors_workspace_bytes, ncf_neighbors.
  * 20: full-catalogue top-K inference: ncf_recommend_workspace_bytes, ncf_recommend,
  * ncf_debug_set_recommend_path.
  * 19: NCF_LAYOUT_FACT_IN_ADAM (0x20) removed -- measured slower than the two launches it
@@ -668,6 +670,47 @@ int ncf_recommend(const ncf_layout *lay, const float *params,
  * sizes) through the materialised path whatever the shape; 0 restores the choice from
  * the layout.  NCF_E_ARG otherwise. */
 int ncf_debug_set_recommend_path(int path);
+
+/*
+ * Nearest neighbours over the learned embeddings: "similar items" / "similar users".
+ * Added within ABI 21 (NCF_ABI_VERSION is unchanged: the addition is purely additive);
+ * probe with dlsym before calling into a library that may predate it.
+ *
+ * For every queries[q] (a row id of the chosen side's table; duplicates allowed; the
+ * caller range-checks them), the top_k best rows of that table, N = user_num or item_num:
+ * ids_out[q * top_k + r] / scores_out[...] is the r-th best.  Order: score descending,
+ * then id ascending -- a total order, and every score is one fixed arithmetic sequence,
+ * so the result does not depend on the tiling, the split or the number of queries.
+ * exclude_self != 0 leaves the query's own id out.  Slots beyond the eligible rows hold
+ * id -1 and score -inf.  1 <= top_k <= 128.  Nothing is allocated or synchronised (the
+ * call can be captured).  A bad side / space / metric / top_k, a null pointer or a
+ * workspace below ncf_neighbors_workspace_bytes returns NCF_E_ARG; n_queries == 0
+ * returns NCF_OK; a vector wider than the LDS budget allows (far beyond the 576 columns
+ * of NCF(64, 4) concat) returns NCF_E_UNSUPPORTED.
+ *
+ * Vector of a row: NCF_SPACE_GMF its embed_*_GMF row (d = factor_num), NCF_SPACE_MLP its
+ * embed_*_MLP row (d = factor_num << (num_layers - 1)), NCF_SPACE_CONCAT the two
+ * concatenated as one vector under one norm.  All three exist for every model_type.
+ * Scores, in fp32 (x = query, c = candidate; each segment zero padded to 16 columns):
+ *   dot    s = sum_i x_i c_i, the fmaf chain  for segment, for t, for r < 4, for g < 4:
+ *          acc = fmaf(x[16 t + 4 g + r], c[16 t + 4 g + r], acc)   (v_mfma_f32_16x16x4_f32)
+ *   cosine s = dot * inv[x] * inv[c], inv[v] = 1 / sqrtf(sum_i v_i^2) (an fmaf chain in
+ *          column order), and inv[v] = 0 where that sum is 0: a zero row scores 0.
+ * Workspace: N floats (inv) and n_queries * splits * top_k (score, id) pairs.
+ * ncf_neighbors_workspace_bytes: bytes of `workspace` for such a call (-1: bad argument).
+ */
+#define NCF_SIDE_USER 0
+#define NCF_SIDE_ITEM 1
+#define NCF_SPACE_GMF 0      /* rows of embed_*_GMF, d = factor_num */
+#define NCF_SPACE_MLP 1      /* rows of embed_*_MLP, d = factor_num << (num_layers-1) */
+#define NCF_SPACE_CONCAT 2   /* [GMF row | MLP row], one vector, one norm */
+#define NCF_SIM_COSINE 0
+#define NCF_SIM_DOT 1
+int64_t ncf_neighbors_workspace_bytes(const ncf_layout *lay, int side, int space, int64_t n_queries, int top_k);
+int ncf_neighbors(const ncf_layout *lay, const float *params, int side, int space, int metric,
+                  const int32_t *queries, int64_t n_queries, int top_k, int exclude_self,
+                  int32_t *ids_out /* [nq][k] */, float *scores_out /* [nq][k] */,
+                  void *workspace, int64_t workspace_bytes, void *stream);
 
 /* Diagnostics only: ablation switches for the next ncf_train_step launches
  * (1 = skip embedding scatter-add, 2 = skip weight-gradient MFMAs).  Results are

@@ -39,6 +39,10 @@ PREP_CANONICAL = 0x1  # ncf_prepare_epoch2 flags: canonical row order inside ite
 PROBE_BLOCKS = 2048  # include/ncf_hip.h NCF_PROBE_BLOCKS (ncf_probe_gather_scatter's sink: x 256 floats)
 LAYOUT_FACT_DEFER_DX = 0x8  # ncf_layout.flags: factored step leaves G for ncf_adam_step_fact (sharded zero1)
 LAYOUT_USER_STORE = 0x10  # ncf_layout.flags (ncf_layout_tune): user-side gradients stored, summed per user
+# ncf_neighbors (added within ABI 21): table side, vector space, similarity
+SIDE_USER, SIDE_ITEM = 0, 1
+SPACE_GMF, SPACE_MLP, SPACE_CONCAT = 0, 1, 2
+SIM_COSINE, SIM_DOT = 0, 1
 MODEL_CODES = {"GMF": MODEL_GMF, "MLP": MODEL_MLP, "NeuMF-end": MODEL_NEUMF, "NeuMF-pre": MODEL_NEUMF}
 
 c_i64 = ctypes.c_int64
@@ -132,6 +136,10 @@ _HIP_PROTOS = {
     "ncf_recommend": (ctypes.c_int, [ctypes.POINTER(NcfLayout), c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_vp, c_vp,
                                      c_vp, c_vp, c_i64, c_vp]),
     "ncf_debug_set_recommend_path": (ctypes.c_int, [ctypes.c_int]),
+    "ncf_neighbors_workspace_bytes": (c_i64, [ctypes.POINTER(NcfLayout), ctypes.c_int, ctypes.c_int, c_i64,
+                                              ctypes.c_int]),
+    "ncf_neighbors": (ctypes.c_int, [ctypes.POINTER(NcfLayout), c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
+                                     c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "ncf_hr_ndcg": (ctypes.c_int, [c_vp, c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "ncf_fact_mode": (ctypes.c_int, [c_vp]),
     "ncf_reduce_rows": (ctypes.c_int, [c_vp]),

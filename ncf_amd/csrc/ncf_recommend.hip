@@ -22,7 +22,9 @@
 // ascending) with a threshold test against its last entry.  The item range is split
 // over workgroups (grid.y); a merge pass orders the partial lists.  The order is total
 // on (score, id) and every score is one fixed arithmetic sequence, so the result does
-// not depend on tiling, the split or the users per workgroup.
+// not depend on tiling, the split or the users per workgroup.  The list insert and the
+// merge pass (rc_feed, rc_list_init, rc_merge_kernel) live in ncf_common.h, shared with
+// ncf_neighbors.hip.
 //
 // Materialised path (the other accepted shapes): user chunks of at most RC_MAT_PAIRS
 // (user, item) pairs -- rows kernel, ncf_forward, select-from-logits with the same
@@ -33,10 +35,7 @@
 
 namespace ncf {
 
-constexpr int RC_WAVES = 4;
 constexpr int RC_CH = 64;  // items per LDS chunk (one seen-mask bit per lane)
-constexpr int RC_MAXK = 128;
-constexpr int RC_IDMAX = 0x7fffffff;      // id of an empty list slot (sorts last)
 constexpr int64_t RC_MAT_PAIRS = 1 << 17;  // materialised path: (user, item) pairs per chunk
 constexpr int RC_LDS_LIMIT = 160 * 1024;
 
@@ -87,46 +86,6 @@ struct RcArgs {
     int nsplit, cps;  // item splits; chunks per split
     int upw;          // users per wave
 };
-
-__device__ __forceinline__ bool rc_better(float s, int id, float ts, int ti) {
-    return s > ts || (s == ts && id < ti);
-}
-
-// Wave-wide insert of the candidates lanes 0..15 hold (ascending ids) into the sorted
-// list ls / li of K entries.  The common case is the one compare against entry K - 1.
-__device__ __forceinline__ void rc_feed(volatile float* ls, volatile int* li, int K, float s, int id, bool valid,
-                                        int lane) {
-    float ts = ls[K - 1];
-    int ti = li[K - 1];
-    unsigned long long m = __ballot(valid && rc_better(s, id, ts, ti));
-    while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        const float cs = __shfl(s, src, 64);
-        const int ci = __shfl(id, src, 64);
-        const int j0 = lane, j1 = lane + 64;
-        float e0s = 0.f, e1s = 0.f;
-        int e0i = 0, e1i = 0;
-        if (j0 < K) { e0s = ls[j0]; e0i = li[j0]; }
-        if (j1 < K) { e1s = ls[j1]; e1i = li[j1]; }
-        const bool b0 = j0 < K && rc_better(e0s, e0i, cs, ci);
-        const bool b1 = j1 < K && rc_better(e1s, e1i, cs, ci);
-        const int pos = __popcll(__ballot(b0)) + __popcll(__ballot(b1));  // entries ahead of the candidate
-        if (j0 < K && !b0 && j0 + 1 < K) { ls[j0 + 1] = e0s; li[j0 + 1] = e0i; }
-        if (j1 < K && !b1 && j1 + 1 < K) { ls[j1 + 1] = e1s; li[j1 + 1] = e1i; }
-        if (lane == 0) { ls[pos] = cs; li[pos] = ci; }
-        ts = ls[K - 1];
-        ti = li[K - 1];
-        m &= m - 1;
-        m &= __ballot(valid && rc_better(s, id, ts, ti));
-    }
-}
-
-__device__ __forceinline__ void rc_list_init(volatile float* ls, volatile int* li, int K, int lane) {
-    for (int j = lane; j < K; j += 64) {
-        ls[j] = -INFINITY;
-        li[j] = RC_IDMAX;
-    }
-}
 
 // First position p in [lo, hi) with seen_items[p] >= item (wave-uniform).
 __device__ __forceinline__ int64_t rc_lower_bound(const int32_t* __restrict__ seen_items, int64_t lo, int64_t hi,
@@ -376,38 +335,6 @@ __global__ __launch_bounds__(RC_WAVES * 64) void rc_kernel(RcArgs a) {
             a.part_s[o + j] = ls[j];
             a.part_i[o + j] = li[j];
         }
-    }
-}
-
-// One wave per user: the nsplit sorted partial lists into the final K (empty slots:
-// item -1, score -inf).
-__global__ __launch_bounds__(RC_WAVES * 64) void rc_merge_kernel(const float* __restrict__ part_s,
-                                                                 const int32_t* __restrict__ part_i, int64_t nq,
-                                                                 int nsplit, int K, int32_t* __restrict__ items_out,
-                                                                 float* __restrict__ scores_out) {
-    extern __shared__ f4 rc_smem4[];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    float* const lsf = reinterpret_cast<float*>(rc_smem4) + wave * 2 * K;
-    int* const lif = reinterpret_cast<int*>(lsf + K);
-    const int64_t q = (int64_t)blockIdx.x * RC_WAVES + wave;
-    if (q >= nq) return;
-    volatile float* ls = lsf;
-    volatile int* li = lif;
-    rc_list_init(ls, li, K, lane);
-    for (int s = 0; s < nsplit; ++s) {
-        const int64_t o = (q * nsplit + s) * K;
-        for (int j0 = 0; j0 < K; j0 += 16) {
-            const int j = j0 + lane;
-            float sc = 0.f;
-            int id = RC_IDMAX;
-            if (lane < 16 && j < K) { sc = part_s[o + j]; id = part_i[o + j]; }
-            rc_feed(ls, li, K, sc, id, id != RC_IDMAX, lane);
-        }
-    }
-    for (int j = lane; j < K; j += 64) {
-        const int id = li[j];
-        items_out[q * K + j] = id == RC_IDMAX ? -1 : id;
-        scores_out[q * K + j] = ls[j];
     }
 }
 
@@ -688,7 +615,7 @@ int ncf_recommend(const ncf_layout* lay, const float* params, const int32_t* use
         if (hipLaunchKernel(e->fn, dim3((unsigned)G.tiles, (unsigned)G.nsplit), dim3(RC_WAVES * 64), args, (size_t)lds,
                             st) != hipSuccess)
             return NCF_E_LAUNCH;
-        hipLaunchKernelGGL(rc_merge_kernel, dim3((unsigned)((n_users + RC_WAVES - 1) / RC_WAVES)), dim3(RC_WAVES * 64),
+        hipLaunchKernelGGL(rc_merge_kernel<>, dim3((unsigned)((n_users + RC_WAVES - 1) / RC_WAVES)), dim3(RC_WAVES * 64),
                            (size_t)RC_WAVES * 2 * K * 4, st, a.part_s, a.part_i, n_users, G.nsplit, K, items_out,
                            scores_out);
         return rc_status();

@@ -202,3 +202,70 @@ class NCF(nn.Module):
             out_i[b:b + c, :m] = torch.where(keep, idx[:, :m], torch.full_like(idx[:, :m], -1))
             out_s[b:b + c, :m] = torch.where(keep, val[:, :m], torch.full_like(val[:, :m], float("-inf")))
         return out_i, out_s
+
+    # ---------------------------------------------------------------- neighbours
+    def similar_items(self, items, k=10, space=None, metric="cosine", exclude_self=True):
+        """The k items whose learned embedding is most similar to each queried item's:
+        ``(ids int64 [Q, k], scores float32 [Q, k])`` on the model's device.  Order:
+        score descending, then id ascending.  ``space``: ``"gmf"`` (rows of
+        ``embed_item_GMF``), ``"mlp"`` (rows of ``embed_item_MLP``) or ``"concat"``;
+        ``None`` is the model's own -- ``"gmf"`` for GMF, ``"mlp"`` for MLP, ``"concat"``
+        for NeuMF-end / NeuMF-pre.  All three exist for every model type (the four
+        tables always do), but a table the model type does not train stays at its
+        initialisation.  Concat is plain concatenation ``[GMF row | MLP row]`` under one
+        norm, so the wider MLP half weighs more.  ``metric``: ``"cosine"`` (a zero row
+        scores 0 against everything) or ``"dot"``.  ``exclude_self`` leaves the queried
+        id out of its own list.  With fewer than k eligible rows the trailing slots hold
+        id -1 and score -inf.  1 <= k <= 128.
+
+        On a HIP device this is ``ncf_neighbors`` (the fused score-and-select kernel);
+        a CPU model runs the same contract with stock torch ops."""
+        return self._similar("item", items, k, space, metric, exclude_self)
+
+    def similar_users(self, users, k=10, space=None, metric="cosine", exclude_self=True):
+        """``similar_items`` over the user tables (``embed_user_GMF`` / ``embed_user_MLP``)."""
+        return self._similar("user", users, k, space, metric, exclude_self)
+
+    def _similar(self, side, queries, k, space, metric, exclude_self):
+        from . import ops
+        k = ops.check_top_k(k)
+        ops.neighbor_codes(self.model_type, side, space, metric)  # ValueError for an unknown name
+        space = ops.default_space(self.model_type) if space is None else space
+        if self.embed_user_GMF.weight.is_cuda:
+            ids, scores = ops.neighbors(self, side, queries, k, space, metric, exclude_self)
+            return ids.to(torch.int64), scores
+        return self._neighbors_cpu(side, queries, k, space, metric, exclude_self)
+
+    @torch.no_grad()
+    def _neighbors_cpu(self, side, queries, k, space, metric, exclude_self, chunk_pairs=1 << 20):
+        gmf = (self.embed_item_GMF if side == "item" else self.embed_user_GMF).weight
+        mlp = (self.embed_item_MLP if side == "item" else self.embed_user_MLP).weight
+        table = {"gmf": gmf, "mlp": mlp}[space] if space != "concat" else torch.cat((gmf, mlp), 1)
+        table = table.detach().to(torch.float32)
+        n = table.shape[0]
+        qi = torch.as_tensor(queries).to(torch.int64).view(-1)
+        if qi.numel() and (int(qi.min()) < 0 or int(qi.max()) >= n):
+            raise IndexError(f"index out of range in self ({side} id)")
+        q = qi.numel()
+        out_i = torch.full((q, k), -1, dtype=torch.int64)
+        out_s = torch.full((q, k), float("-inf"), dtype=torch.float32)
+        if metric == "cosine":
+            ss = (table * table).sum(1)
+            inv = torch.where(ss > 0, 1.0 / torch.sqrt(ss), torch.zeros_like(ss))
+        m = min(k, n)
+        eligible = n - 1 if exclude_self else n
+        step = max(1, chunk_pairs // n)
+        for b in range(0, q, step):
+            ids = qi[b:b + step]
+            c = ids.numel()
+            s = table[ids] @ table.t()
+            if metric == "cosine":
+                s = s * inv[ids].unsqueeze(1) * inv.unsqueeze(0)
+            if exclude_self:
+                s[torch.arange(c), ids] = float("-inf")
+            # stable: equal scores keep ascending ids; the excluded id sorts last
+            val, idx = torch.sort(s, dim=1, descending=True, stable=True)
+            keep = (torch.arange(m) < eligible).unsqueeze(0).expand(c, m)
+            out_i[b:b + c, :m] = torch.where(keep, idx[:, :m], torch.full_like(idx[:, :m], -1))
+            out_s[b:b + c, :m] = torch.where(keep, val[:, :m], torch.full_like(val[:, :m], float("-inf")))
+        return out_i, out_s

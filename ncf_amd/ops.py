@@ -575,3 +575,66 @@ def recommend(model, users, k, seen=None):
     ws = recommend_workspace(lay, q, k, model, dev)
     recommend_into(flat, lay, u, k, seen, items, scores, ws)
     return items, scores
+
+
+# ---------------------------------------------------------------------------
+# nearest neighbours over the embedding tables (ncf_neighbors; added within ABI 21)
+SIDES = {"user": L.SIDE_USER, "item": L.SIDE_ITEM}
+SPACES = {"gmf": L.SPACE_GMF, "mlp": L.SPACE_MLP, "concat": L.SPACE_CONCAT}
+METRICS = {"cosine": L.SIM_COSINE, "dot": L.SIM_DOT}
+
+
+def default_space(model_type):
+    """The space a model of this type scores with: its own tables."""
+    return {"GMF": "gmf", "MLP": "mlp"}.get(model_type, "concat")
+
+
+def neighbor_codes(model_type, side, space, metric):
+    """(side, space, metric) names -> the C ABI's codes; ValueError for an unknown one."""
+    if space is None:
+        space = default_space(model_type)
+    for what, value, table in (("side", side, SIDES), ("space", space, SPACES), ("metric", metric, METRICS)):
+        if not isinstance(value, str) or value not in table:
+            raise ValueError(f"unknown {what} {value!r}: one of {sorted(table)}")
+    return SIDES[side], SPACES[space], METRICS[metric]
+
+
+def neighbors_workspace(lay, side, space, n_queries, k, owner, dev):
+    need = int(L.hip().ncf_neighbors_workspace_bytes(L.ctypes.byref(lay), int(side), int(space), int(n_queries),
+                                                     int(k)))
+    if need < 0:
+        raise ValueError("ncf_neighbors_workspace_bytes failed")
+    return _ws(owner, "_ncf_nb_ws", need, dev)
+
+
+def neighbors_into(flat, lay, side, space, metric, q_i32, k, exclude_self, ids_out, scores_out, ws):
+    """One ncf_neighbors call on the current stream into preallocated tensors
+    (capturable: nothing is allocated or synchronised)."""
+    L.check(L.hip().ncf_neighbors(L.ctypes.byref(lay), flat.data_ptr(), int(side), int(space), int(metric),
+                                  q_i32.data_ptr(), q_i32.numel(), int(k), 1 if exclude_self else 0,
+                                  ids_out.data_ptr(), scores_out.data_ptr(),
+                                  None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
+                                  L.stream_ptr(flat.device)), "ncf_neighbors")
+
+
+def neighbors(model, side, queries, k, space=None, metric="cosine", exclude_self=True):
+    """(ids int32 [Q, k], scores float32 [Q, k]) of a HIP-resident model: the k rows of
+    the `side` ("item" / "user") embedding table most similar to every queried row, score
+    descending then id ascending, -1 / -inf in unfilled slots.  `space`: "gmf", "mlp" or
+    "concat" (None: default_space(model.model_type)); `metric`: "cosine" or "dot"."""
+    k = check_top_k(k)
+    side_c, space_c, metric_c = neighbor_codes(model.model_type, side, space, metric)
+    flat, lay = ensure_flat(model)
+    dev = flat.device
+    q = _as_i32(queries, dev).view(-1)
+    n = q.numel()
+    ids = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    if n == 0:
+        return ids, scores
+    lo, hi = torch.stack([q.min(), q.max()]).tolist()
+    if lo < 0 or hi >= (model.item_num if side == "item" else model.user_num):
+        raise IndexError(f"index out of range in self ({side} id)")
+    ws = neighbors_workspace(lay, side_c, space_c, n, k, model, dev)
+    neighbors_into(flat, lay, side_c, space_c, metric_c, q, k, exclude_self, ids, scores, ws)
+    return ids, scores

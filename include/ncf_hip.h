@@ -23,7 +23,8 @@ extern "C" {
 
 /* 21: pairwise (BPR) training: NCF_DZ_BPR of ncf_train_step, ncf_build_pair_stream.
  * Added within 21 (purely additive, the version is unchanged; probe with dlsym):
- * ncf_neighbors_workspace_bytes, ncf_neighbors.
+ * ncf_neighbors_workspace_bytes, ncf_neighbors; ncf_fold_opt, ncf_fold_in_workspace_bytes,
+ * ncf_fold_in, ncf_debug_set_fold_path.
  * 20: full-catalogue top-K inference: ncf_recommend_workspace_bytes, ncf_recommend,
  * ncf_debug_set_recommend_path.
  * 19: NCF_LAYOUT_FACT_IN_ADAM (0x20) removed -- measured slower than the two launches it
@@ -711,6 +712,66 @@ int ncf_neighbors(const ncf_layout *lay, const float *params, int side, int spac
                   const int32_t *queries, int64_t n_queries, int top_k, int exclude_self,
                   int32_t *ids_out /* [nq][k] */, float *scores_out /* [nq][k] */,
                   void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
+ * Fold-in: vectors for users that were not in the training set, fitted to their
+ * interaction lists.  Added within ABI 21 (NCF_ABI_VERSION is unchanged: the addition is
+ * purely additive); probe with dlsym before calling into a library that may predate it.
+ * The reference has nothing of the kind (a new user means retraining); like ncf_recommend
+ * it stands next to the reference surface.
+ *
+ * The item tables, the tower and the predict layer are frozen.  For folded user q the
+ * examples are e in [ex_ptr[q], ex_ptr[q + 1]) with ex_items[e] (the caller range-checks
+ * the ids, as for ncf_forward) and ex_labels[e] in [0, 1], in the caller's order, and
+ *   loss_q(ug, um) = mean_e BCEWithLogits(logit(ug, um, ex_items[e]), ex_labels[e]),
+ * logit being NCF.forward in eval mode (models.py:97-118; dropout never applies) with the
+ * user's embed_user_GMF / embed_user_MLP rows replaced by ug [f] / um [dm],
+ * dm = factor_num << (num_layers - 1).  A user with no examples has loss 0 and gradient 0.
+ * The optimiser is torch.optim.Adam (not AdamW) on the f + dm floats (ug | um) of each
+ * user: opt->steps >= 1 full-batch steps t = t0 + 1 .. t0 + steps with
+ *   g = d loss_q / d(ug | um) + weight_decay * (ug | um)
+ * and the arithmetic of ncf_adam_step (the same operations, the same bits).  Model type
+ * GMF: only ug has a gradient, um and its state come back untouched; MLP: only um; NeuMF:
+ * both.  grad_out holds 0 in the half a model type does not train.
+ *
+ * ug / um: in the start vectors, out the result.  exp_avg / exp_avg_sq [n][f + dm]: in / out
+ * Adam state; both NULL: start from zero and discard.  loss_out[q][s]: the loss at the
+ * vectors before step s's update.  grad_out[q]: g of the last step.  A user's result is a
+ * function of its own examples (in the given order), its start vectors and state and the
+ * hyper-parameters: it does not depend on the other users of the call, their number or the
+ * user's position (every reduction has a fixed order).
+ *
+ * One prologue launch (Pi = Im W0[:, dm:]^T + b0 over the catalogue and the step scalars)
+ * and one kernel with a workgroup per user that runs all the steps.  NCF_PATH_FUSED shapes
+ * with dm <= 64: weights in LDS, the tower forward and backward on MFMA tiles in registers.
+ * Other shapes: plain fp32 loops (coverage, not speed).  In calls of at most 16,384 users
+ * the workgroups take the users longest list first (the prologue ranks them); no result
+ * depends on that.  Workspace: item_num * max(16, dm) (generic path: dm; GMF: 0) floats,
+ * 2 * steps floats and, up to 16,384 users, n_users int32, each rounded up to 256 bytes.
+ * Nothing is allocated or synchronised (the call can be captured).  NCF_E_ARG: a null
+ * required pointer, steps < 1, t0 < 0, a negative count, only one of the two state
+ * pointers, a workspace below ncf_fold_in_workspace_bytes (-1 from that: bad argument).
+ * n_users == 0 returns NCF_OK with nothing launched.
+ */
+typedef struct ncf_fold_opt {
+    double lr, beta1, beta2;
+    float eps, weight_decay;
+    int32_t steps;
+    int64_t t0;
+} ncf_fold_opt;
+int64_t ncf_fold_in_workspace_bytes(const ncf_layout *lay, int64_t n_users, int64_t n_examples, int steps);
+int ncf_fold_in(const ncf_layout *lay, const float *params,
+                const int64_t *ex_ptr /* n_users + 1 */, const int32_t *ex_items, const float *ex_labels,
+                int64_t n_users, int64_t n_examples,
+                float *ug /* [n][f] */, float *um /* [n][dm] */,
+                float *exp_avg, float *exp_avg_sq /* [n][f + dm] or both NULL */,
+                const ncf_fold_opt *opt,
+                float *loss_out /* [n][steps] or NULL */, float *grad_out /* [n][f + dm] or NULL */,
+                void *workspace, int64_t workspace_bytes, void *stream);
+/* Tests only: NCF_PATH_LAYERED sends later ncf_fold_in calls (and their workspace sizes)
+ * through the generic path whatever the shape; 0 restores the choice from the layout.
+ * NCF_E_ARG otherwise. */
+int ncf_debug_set_fold_path(int path);
 
 /* Diagnostics only: ablation switches for the next ncf_train_step launches
  * (1 = skip embedding scatter-add, 2 = skip weight-gradient MFMAs).  Results are

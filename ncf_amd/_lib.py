@@ -83,6 +83,12 @@ class NcfAisBufs(ctypes.Structure):
                 ("grads_2", c_vp), ("state", c_vp)]
 
 
+class NcfFoldOpt(ctypes.Structure):
+    """include/ncf_hip.h ncf_fold_opt (ncf_fold_in; added within ABI 21)."""
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_float), ("weight_decay", ctypes.c_float), ("steps", c_i32), ("t0", c_i64)]
+
+
 _OWNER = ctypes.POINTER(NcfOwnerPlan)
 _AIS = ctypes.POINTER(NcfAisBufs)
 _LAY = ctypes.POINTER(NcfLayout)
@@ -140,6 +146,10 @@ _HIP_PROTOS = {
                                               ctypes.c_int]),
     "ncf_neighbors": (ctypes.c_int, [ctypes.POINTER(NcfLayout), c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
                                      c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "ncf_fold_in_workspace_bytes": (c_i64, [ctypes.POINTER(NcfLayout), c_i64, c_i64, ctypes.c_int]),
+    "ncf_fold_in": (ctypes.c_int, [ctypes.POINTER(NcfLayout), c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,
+                                   c_vp, ctypes.POINTER(NcfFoldOpt), c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "ncf_debug_set_fold_path": (ctypes.c_int, [ctypes.c_int]),
     "ncf_hr_ndcg": (ctypes.c_int, [c_vp, c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "ncf_fact_mode": (ctypes.c_int, [c_vp]),
     "ncf_reduce_rows": (ctypes.c_int, [c_vp]),

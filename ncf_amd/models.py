@@ -269,3 +269,136 @@ class NCF(nn.Module):
             out_i[b:b + c, :m] = torch.where(keep, idx[:, :m], torch.full_like(idx[:, :m], -1))
             out_s[b:b + c, :m] = torch.where(keep, val[:, :m], torch.full_like(val[:, :m], float("-inf")))
         return out_i, out_s
+
+    # ------------------------------------------------------------------ fold-in
+    def fold_in(self, examples, steps=50, lr=0.01, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, init="mean",
+                state=None):
+        """Vectors for users that were not in the training set, fitted to their interaction
+        lists with everything else frozen: ``ops.FoldedUsers(gmf [Q, f], mlp [Q, dm],
+        loss [Q, steps], state)`` on the model's device.
+
+        ``examples``: an ``ops.FoldExamples`` (``ops.fold_examples`` builds one from
+        interaction lists with sampled negatives).  Per user, ``steps`` full-batch
+        ``torch.optim.Adam`` steps on its two vectors of the mean ``BCEWithLogits`` over its
+        examples of ``forward`` in eval mode (dropout never applies); ``weight_decay`` is
+        Adam's (added to the gradient).  A GMF model fits only ``gmf``, an MLP model only
+        ``mlp`` (the other half comes back as initialised).  ``loss[q, s]`` is the loss at
+        the vectors before step s's update; a user without examples has loss 0 and stays
+        where it started.  ``init``: ``"mean"`` (the column means of the user tables),
+        ``"zeros"`` or a ``(gmf, mlp)`` pair of start vectors.  ``state``: the
+        ``ops.FoldState`` of an earlier call to continue from (None: a fresh optimizer).
+        A user's result does not depend on the other users of the call.
+
+        On a HIP device this is ``ncf_fold_in`` (one kernel runs every step of a user);
+        a CPU model runs the same contract with stock torch autograd and
+        ``torch.optim.Adam``.  Serve the result with ``with_users``."""
+        from . import ops
+        steps = ops.check_fold_steps(steps)
+        ex = ops.check_fold_examples(examples, self.item_num)
+        q = ex.ptr.numel() - 1
+        gmf0, mlp0 = self._fold_init(init, q)
+        if self.embed_user_GMF.weight.is_cuda:
+            return ops.fold_in(self, ex, gmf0, mlp0, steps, lr, betas, eps, weight_decay, state)
+        return self._fold_in_cpu(ex, gmf0, mlp0, steps, lr, betas, eps, weight_decay, state)
+
+    def _fold_init(self, init, q):
+        ug, um = self.embed_user_GMF.weight.detach(), self.embed_user_MLP.weight.detach()
+        if isinstance(init, str):
+            if init == "mean":
+                return ug.mean(0, keepdim=True).repeat(q, 1), um.mean(0, keepdim=True).repeat(q, 1)
+            if init == "zeros":
+                return ug.new_zeros((q, ug.shape[1])), um.new_zeros((q, um.shape[1]))
+            raise ValueError(f"unknown init {init!r}: 'mean', 'zeros' or a (gmf, mlp) pair")
+        try:
+            g, m = init
+            g = torch.as_tensor(g, dtype=torch.float32).to(ug.device)
+            m = torch.as_tensor(m, dtype=torch.float32).to(ug.device)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"unknown init {init!r}: 'mean', 'zeros' or a (gmf, mlp) pair") from e
+        if g.shape != (q, ug.shape[1]) or m.shape != (q, um.shape[1]):
+            raise ValueError("init: the start vectors must be gmf [Q, f] and mlp [Q, dm]")
+        return g, m
+
+    def _logits_vectors(self, ug, um, item):
+        """_logits_eval with the user rows given per example."""
+        def tower(x):
+            for lin in self.linear_layers():
+                x = torch.relu(lin(x))
+            return x
+        if self.model_type == "GMF":
+            output = ug * self.embed_item_GMF(item)
+        elif self.model_type == "MLP":
+            output = tower(torch.cat((um, self.embed_item_MLP(item)), -1))
+        else:
+            output = torch.cat((ug * self.embed_item_GMF(item),
+                                tower(torch.cat((um, self.embed_item_MLP(item)), -1))), -1)
+        return self.predict_layer(output).view(-1)
+
+    def _fold_in_cpu(self, ex, gmf0, mlp0, steps, lr, betas, eps, weight_decay, state):
+        from . import ops
+        q = ex.ptr.numel() - 1
+        f = gmf0.shape[1]
+        counts = (ex.ptr[1:] - ex.ptr[:-1])
+        owner = torch.repeat_interleave(torch.arange(q), counts)
+        weight = (1.0 / counts.clamp(min=1).to(torch.float32))[owner]
+        items = ex.items.to(torch.int64)
+        gmf = gmf0.detach().to(torch.float32).clone().requires_grad_(self.model_type != "MLP")
+        mlp = mlp0.detach().to(torch.float32).clone().requires_grad_(self.model_type != "GMF")
+        trained = [p for p in (gmf, mlp) if p.requires_grad]
+        opt = torch.optim.Adam(trained, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        width = f + mlp.shape[1]
+        m = torch.zeros((q, width)) if state is None else state.exp_avg.detach().to("cpu", torch.float32).clone()
+        v = torch.zeros((q, width)) if state is None else state.exp_avg_sq.detach().to("cpu", torch.float32).clone()
+        t0 = 0 if state is None else int(state.step)
+        if m.shape != (q, width) or v.shape != (q, width) or t0 < 0:
+            raise ValueError("fold-in state: exp_avg / exp_avg_sq must be [Q, f + dm] and step >= 0")
+        cols = {id(gmf): slice(0, f), id(mlp): slice(f, width)}
+        for p in trained:
+            opt.state[p] = {"step": torch.tensor(float(t0)), "exp_avg": m[:, cols[id(p)]].clone(),
+                            "exp_avg_sq": v[:, cols[id(p)]].clone()}
+        loss = torch.zeros((q, steps))
+        frozen = [(p, p.requires_grad) for p in self.parameters()]
+        for p, _ in frozen:
+            p.requires_grad_(False)
+        try:
+            for s in range(steps):
+                opt.zero_grad(set_to_none=True)
+                z = self._logits_vectors(gmf[owner], mlp[owner], items)
+                per = torch.nn.functional.binary_cross_entropy_with_logits(z, ex.labels, reduction="none") * weight
+                loss[:, s] = torch.zeros(q).index_add_(0, owner, per.detach())
+                if per.numel():
+                    per.sum().backward()
+                for p in trained:  # a call without examples still runs Adam with g = wd * p
+                    if p.grad is None:
+                        p.grad = torch.zeros_like(p)
+                opt.step()
+        finally:
+            for p, r in frozen:
+                p.requires_grad_(r)
+        for p in trained:
+            m[:, cols[id(p)]] = opt.state[p]["exp_avg"]
+            v[:, cols[id(p)]] = opt.state[p]["exp_avg_sq"]
+        return ops.FoldedUsers(gmf.detach(), mlp.detach(), loss, ops.FoldState(m, v, t0 + steps))
+
+    def with_users(self, folded):
+        """A new NCF of the same type and shape on the same device whose user tables are the
+        folded vectors (``user_num = Q``; ``folded``: an ``ops.FoldedUsers`` or a
+        ``(gmf, mlp)`` pair) and whose other parameters are copies of this model's, so
+        ``forward``, ``recommend``, ``similar_users`` and the evaluators serve folded users
+        as user ids 0 .. Q - 1."""
+        gmf, mlp = (folded.gmf, folded.mlp) if hasattr(folded, "gmf") else folded
+        ug, um = self.embed_user_GMF.weight, self.embed_user_MLP.weight
+        if gmf.dim() != 2 or mlp.dim() != 2 or gmf.shape[0] != mlp.shape[0] or gmf.shape[0] < 1 \
+                or gmf.shape[1] != ug.shape[1] or mlp.shape[1] != um.shape[1]:
+            raise ValueError("with_users: needs gmf [Q, f] and mlp [Q, dm] with Q >= 1")
+        with torch.random.fork_rng(devices=[]):  # the constructor's initialisation draws are discarded
+            new = NCF(gmf.shape[0], self.item_num, self.factor_num, self.num_layers, self.dropout, self.model_type)
+        new = new.to(ug.device)
+        with torch.no_grad():
+            for dst, src in zip(new.ordered_params()[:4], (gmf, self.embed_item_GMF.weight, mlp,
+                                                           self.embed_item_MLP.weight)):
+                dst.copy_(src.detach().to(dst.device))
+            for dst, src in zip(new.ordered_params()[4:], self.ordered_params()[4:]):
+                dst.copy_(src.detach())
+        new.train(self.training)
+        return new

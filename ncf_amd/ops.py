@@ -638,3 +638,163 @@ def neighbors(model, side, queries, k, space=None, metric="cosine", exclude_self
     ws = neighbors_workspace(lay, side_c, space_c, n, k, model, dev)
     neighbors_into(flat, lay, side_c, space_c, metric_c, q, k, exclude_self, ids, scores, ws)
     return ids, scores
+
+
+# ---------------------------------------------------------------------------
+# fold-in: vectors for unseen users from their interaction lists (ncf_fold_in; added within ABI 21)
+class FoldExamples(collections.namedtuple("FoldExamples", "ptr items labels")):
+    """Examples of Q folded users: ptr int64 [Q + 1], items int32 [E], labels float32 [E]
+    in [0, 1]; user q owns the examples ptr[q] .. ptr[q + 1], in that order."""
+    __slots__ = ()
+
+
+class FoldState(collections.namedtuple("FoldState", "exp_avg exp_avg_sq step")):
+    """Adam state of folded users: exp_avg / exp_avg_sq float32 [Q, f + dm] over (gmf | mlp),
+    step = the optimizer steps taken so far."""
+    __slots__ = ()
+
+
+class FoldedUsers(collections.namedtuple("FoldedUsers", "gmf mlp loss state")):
+    """Result of NCF.fold_in: gmf [Q, f], mlp [Q, dm], loss [Q, steps] (the loss at the
+    vectors before each step's update) and the FoldState to continue from."""
+    __slots__ = ()
+
+
+def _np_i64(x):
+    return np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x).astype(np.int64).reshape(-1)
+
+
+def _histories(histories):
+    """list of item-id sequences / (users, items) pair / SeenCSR -> list of int64 arrays.
+    A pair groups the items by user id 0 .. max(users), each user's in order of appearance."""
+    if isinstance(histories, SeenCSR):
+        ptr, items = _np_i64(histories.ptr), _np_i64(histories.items)
+        return [items[ptr[q]:ptr[q + 1]] for q in range(len(ptr) - 1)]
+    if isinstance(histories, tuple) and len(histories) == 2:
+        u, i = _np_i64(histories[0]), _np_i64(histories[1])
+        if u.size != i.size:
+            raise ValueError("fold_examples: users and items must have equal length")
+        if u.size and int(u.min()) < 0:
+            raise IndexError("index out of range in self (user id)")
+        q = int(u.max()) + 1 if u.size else 0
+        order = np.argsort(u, kind="stable")
+        cuts = np.cumsum(np.bincount(u, minlength=q))[:-1] if q else []
+        return list(np.split(i[order], cuts)) if q else []
+    return [_np_i64(h) for h in histories]
+
+
+def fold_examples(histories, item_num, num_ng=4, generator=None):
+    """FoldExamples (CPU tensors) of the users' interaction lists: per user the given items
+    as positives (label 1), then num_ng * len negatives (label 0) drawn uniformly from the
+    items not in that user's list with a CPU torch.Generator (None: the default one).
+    `histories`: a list of item-id sequences, a (users, items) pair of arrays (user ids
+    0 .. max) or a SeenCSR.  ValueError if a list covers the catalogue."""
+    item_num, num_ng = int(item_num), int(num_ng)
+    if num_ng < 0:
+        raise ValueError("fold_examples: num_ng must be >= 0")
+    ptr, items, labels = [0], [], []
+    for h in _histories(histories):
+        if h.size and (int(h.min()) < 0 or int(h.max()) >= item_num):
+            raise IndexError("index out of range in self (item id)")
+        members = np.unique(h)
+        free = item_num - members.size
+        if free <= 0:
+            raise ValueError("fold_examples: an interaction list covers the whole catalogue")
+        n_neg = num_ng * h.size
+        r = torch.randint(0, free, (n_neg,), generator=generator, dtype=torch.int64).numpy()
+        # the r-th item that is not a member: members m_j shift every rank >= m_j - j by one
+        neg = r + np.searchsorted(members - np.arange(members.size), r, side="right")
+        items += [h, neg]
+        labels += [np.ones(h.size, np.float32), np.zeros(n_neg, np.float32)]
+        ptr.append(ptr[-1] + h.size + n_neg)
+    cat = np.concatenate(items).astype(np.int32) if items else np.zeros(0, np.int32)
+    lab = np.concatenate(labels) if labels else np.zeros(0, np.float32)
+    return FoldExamples(torch.from_numpy(np.asarray(ptr, dtype=np.int64)), torch.from_numpy(cat),
+                        torch.from_numpy(lab))
+
+
+def check_fold_examples(ex, item_num):
+    """FoldExamples with the right dtypes and contents (ValueError / IndexError otherwise)."""
+    ptr = torch.as_tensor(ex.ptr).to(torch.int64).view(-1)
+    items = torch.as_tensor(ex.items).view(-1)
+    labels = torch.as_tensor(ex.labels).to(torch.float32).view(-1)
+    if ptr.numel() < 1 or items.numel() != labels.numel():
+        raise ValueError("fold-in examples: ptr needs Q + 1 entries, items and labels equal length")
+    p = ptr.cpu()
+    if int(p[0]) != 0 or int(p[-1]) != items.numel() or (p.numel() > 1 and bool((p[1:] < p[:-1]).any())):
+        raise ValueError("fold-in examples: ptr must ascend from 0 to the number of examples")
+    if items.numel():
+        lo, hi = int(items.min()), int(items.max())
+        if lo < 0 or hi >= item_num:
+            raise IndexError("index out of range in self (item id)")
+        if float(labels.min()) < 0.0 or float(labels.max()) > 1.0 or bool(torch.isnan(labels).any()):
+            raise ValueError("fold-in examples: labels must lie in [0, 1]")
+    return FoldExamples(ptr, items.to(torch.int32), labels)
+
+
+def check_fold_steps(steps):
+    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
+        raise ValueError(f"fold-in steps must be an integer >= 1, got {steps!r}")
+    return int(steps)
+
+
+def fold_opt(steps, lr, betas, eps, weight_decay, t0=0):
+    return L.NcfFoldOpt(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(steps),
+                        int(t0))
+
+
+@contextlib.contextmanager
+def _fold_generic():
+    """Tests: ncf_fold_in through its generic path whatever the shape."""
+    L.check(L.hip().ncf_debug_set_fold_path(L.PATH_LAYERED), "ncf_debug_set_fold_path")
+    try:
+        yield
+    finally:
+        L.hip().ncf_debug_set_fold_path(0)
+
+
+def fold_in_workspace(lay, n_users, n_examples, steps, owner, dev):
+    need = int(L.hip().ncf_fold_in_workspace_bytes(L.ctypes.byref(lay), int(n_users), int(n_examples), int(steps)))
+    if need < 0:
+        raise ValueError("ncf_fold_in_workspace_bytes failed")
+    return _ws(owner, "_ncf_fold_ws", need, dev)
+
+
+def fold_in_into(flat, lay, ex, gmf, mlp, exp_avg, exp_avg_sq, opt, loss_out, grad_out, ws):
+    """One ncf_fold_in call on the current stream, in place on gmf / mlp (and the Adam
+    state, if given) with preallocated outputs (capturable: nothing is allocated or
+    synchronised).  `ex`: FoldExamples on the device; `opt`: fold_opt(...)."""
+    L.check(L.hip().ncf_fold_in(L.ctypes.byref(lay), flat.data_ptr(), ex.ptr.data_ptr(), L.ptr(ex.items) or None,
+                                L.ptr(ex.labels) or None, ex.ptr.numel() - 1, ex.items.numel(),
+                                gmf.data_ptr(), mlp.data_ptr(), L.ptr(exp_avg), L.ptr(exp_avg_sq),
+                                L.ctypes.byref(opt), L.ptr(loss_out), L.ptr(grad_out),
+                                None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
+                                L.stream_ptr(flat.device)), "ncf_fold_in")
+
+
+def fold_in(model, ex, gmf0, mlp0, steps, lr, betas, eps, weight_decay, state=None, grad_out=None):
+    """FoldedUsers of a HIP-resident model from checked examples and start vectors
+    (copied, not modified)."""
+    flat, lay = ensure_flat(model)
+    dev = flat.device
+    ex = FoldExamples(ex.ptr.to(dev).contiguous(), ex.items.to(dev).contiguous(), ex.labels.to(dev).contiguous())
+    q = ex.ptr.numel() - 1
+    gmf = gmf0.to(device=dev, dtype=torch.float32).clone().contiguous()
+    mlp = mlp0.to(device=dev, dtype=torch.float32).clone().contiguous()
+    width = gmf.shape[1] + mlp.shape[1]
+    if state is None:
+        m = torch.zeros((q, width), dtype=torch.float32, device=dev)
+        v = torch.zeros((q, width), dtype=torch.float32, device=dev)
+        t0 = 0
+    else:
+        m = state.exp_avg.to(device=dev, dtype=torch.float32).clone().contiguous()
+        v = state.exp_avg_sq.to(device=dev, dtype=torch.float32).clone().contiguous()
+        t0 = int(state.step)
+        if m.shape != (q, width) or v.shape != (q, width) or t0 < 0:
+            raise ValueError("fold-in state: exp_avg / exp_avg_sq must be [Q, f + dm] and step >= 0")
+    loss = torch.zeros((q, steps), dtype=torch.float32, device=dev)
+    if q:
+        ws = fold_in_workspace(lay, q, ex.items.numel(), steps, model, dev)
+        fold_in_into(flat, lay, ex, gmf, mlp, m, v, fold_opt(steps, lr, betas, eps, weight_decay, t0), loss, grad_out,
+                     ws)
+    return FoldedUsers(gmf, mlp, loss, FoldState(m, v, t0 + steps))

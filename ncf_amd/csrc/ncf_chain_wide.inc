@@ -19,7 +19,7 @@
 // no activation ever goes through LDS.
 //
 // Precision.  fp32 products on the bf16 cores by the exact three-plane split of
-// gemm_block_x6s (ncf_layered.hip): x = h + m + l, six products per pair, smallest
+// ncf_gemm.h (x6_frag, x6_mma): x = h + m + l, six products per pair, smallest
 // terms first.  The weights are split once per staged chunk (per tile), the
 // activations once per K step (per wave) and reused across the K step's 16 tiles.
 //
@@ -59,7 +59,7 @@ constexpr int PREP_THREADS = NCH * 16 * 64;  // one thread per (chunk, K step x 
 // W0 as the pre-split B operand of the projection and the dX expansion (gemm_block_x6b):
 // four images (projection users / items, dX users / items), each [n group of 16][K step
 // of 32][plane][lane] x 16 B -- lane l of (ng, ks) holds B[32 ks + 8 (l >> 4) .. + 7]
-// [16 ng + (l & 15)] (x6s_frag's K order)
+// [16 ng + (l & 15)] (x6s_frag's K order, ncf_gemm.h)
 constexpr int W0_NG = DM / 16, W0_KS = DM / 32;
 constexpr int64_t W0_NG_BYTES = (int64_t)W0_KS * 3 * 1024;          // one n group
 constexpr int64_t W0_IMG_BYTES = (int64_t)W0_NG * W0_NG_BYTES;      // one image (1.5 MB)
@@ -80,18 +80,6 @@ __device__ __forceinline__ void stage(const char* img, int local, char* lds, int
     }
 }
 
-// the B operand of one K step from 8 fp32 values (x: tile 2 s, y: tile 2 s + 1)
-__device__ __forceinline__ void bfrag(const f4& x, const f4& y, bf16x8 (&f)[3]) {
-    uint4 h, m, lo;
-    split3(x.x, x.y, h.x, m.x, lo.x);
-    split3(x.z, x.w, h.y, m.y, lo.y);
-    split3(y.x, y.y, h.z, m.z, lo.z);
-    split3(y.z, y.w, h.w, m.w, lo.w);
-    f[0] = __builtin_bit_cast(bf16x8, h);
-    f[1] = __builtin_bit_cast(bf16x8, m);
-    f[2] = __builtin_bit_cast(bf16x8, lo);
-}
-
 // acc[mt] += A(tile mt of the K step at `buf`) B for the wave's 16 rows, six products
 // smallest first
 template <int MT>
@@ -108,14 +96,7 @@ __device__ __forceinline__ void kstep(const char* buf, int l, const bf16x8 (&b)[
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         if (mt + 1 < MT) rd(mt + 1, fa[(mt + 1) & 1]);
-        const bf16x8(&a)[3] = fa[mt & 1];
-        f4 cc = acc[mt];
-        cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], cc, 0, 0, 0);
-        cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], cc, 0, 0, 0);
-        cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], cc, 0, 0, 0);
-        cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], cc, 0, 0, 0);
-        cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], cc, 0, 0, 0);
-        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], cc, 0, 0, 0);
+        acc[mt] = x6_mma(fa[mt & 1], b, acc[mt]);
         if (mt + 1 < MT) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -301,7 +282,7 @@ __global__ __launch_bounds__(wc::NT) void lyr_wide_chain_kernel(LyrArgs a, const
                 mb1 = (mb1 << 8) | (mb0 >> 24);
                 mb0 = (mb0 << 8) | pos_bits(x) | (pos_bits(y) << 4);
                 bf16x8 bf[3];
-                bfrag(x, y, bf);
+                x6_frag(x, y, bf);
                 kstep<16>(buf(cid), l, bf, acc);
                 WC_END();
             }
@@ -327,7 +308,7 @@ __global__ __launch_bounds__(wc::NT) void lyr_wide_chain_kernel(LyrArgs a, const
 #pragma unroll 1
                 for (int ksl = 0; ksl < 2; ++ksl) {
                     bf16x8 bf[3];
-                    bfrag(h2[0], h2[1], bf);
+                    x6_frag(h2[0], h2[1], bf);
                     rotate2(h2);
                     kstep<8>(buf(cid) + img_off(8, ksl, 0, 0), l, bf, acc);
                 }
@@ -359,7 +340,7 @@ WC_BEGIN();
 #pragma unroll 1
             for (int ksl = 0; ksl < 4; ++ksl) {
                 bf16x8 bf[3];
-                bfrag(h3[0], h3[1], bf);
+                x6_frag(h3[0], h3[1], bf);
                 rotate2(h3);
                 kstep<4>(buf(cid) + img_off(4, ksl, 0, 0), l, bf, acc);
             }
@@ -477,7 +458,7 @@ WC_BEGIN();
 #pragma unroll 1
             for (int ksl = 0; ksl < 2; ++ksl) {
                 bf16x8 bf[3];
-                bfrag(d3[0], d3[1], bf);
+                x6_frag(d3[0], d3[1], bf);
                 rotate2(d3);
                 kstep<8>(buf(cid) + img_off(8, ksl, 0, 0), l, bf, acc);
             }
@@ -498,7 +479,7 @@ WC_BEGIN();
             for (int ks = 0; ks < 4; ++ks) {
                 WC_BEGIN();
                 bf16x8 bf[3];
-                bfrag(d2[0], d2[1], bf);
+                x6_frag(d2[0], d2[1], bf);
                 rotate2(d2);
                 kstep<16>(buf(cid), l, bf, acc);
                 WC_END();
@@ -520,7 +501,7 @@ WC_BEGIN();
             for (int ks = 0; ks < 8; ++ks) {
                 WC_BEGIN();
                 bf16x8 bf[3];
-                bfrag(d1[0], d1[1], bf);
+                x6_frag(d1[0], d1[1], bf);
                 rotate2(d1);  // cyclic: both groups read D_1 from the front
                 kstep<16>(buf(cid), l, bf, acc);
                 WC_END();

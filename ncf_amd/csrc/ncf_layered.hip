@@ -23,21 +23,33 @@
 // and fact_expand_kernel (ncf_fact.hip) turns those per-row-sum rows into dUm, dIm
 // and the dW0 partials -- three (U + I)-row GEMMs in place of three B-row ones.
 //
-// All three GEMM shapes run on one MFMA core: v_mfma_f32_16x16x4f32 (exact
-// fp32), 256 threads = 4 waves, 64x64 block tile, each wave a 32x32 sub-tile
-// (2x2 MFMA tiles), K in steps of 16 through double-buffered LDS.  Operand
-// loaders map lanes along the operand's contiguous memory dimension.  Rows at
-// or past the batch's end are padding: they gather id 0 and their dz is 0, so
-// every gradient contribution from them is zero.
+// All the GEMM shapes run on the block-tile cores of ncf_gemm.h: 256 threads = 4
+// waves, a 64 x 64 (or 128 x 128) block tile, K through double-buffered LDS, exact
+// fp32 MFMAs or the bf16 three-plane split.  Operand loaders map lanes along the
+// operand's contiguous memory dimension.  Rows at or past the batch's end are
+// padding: they gather id 0 and their dz is 0, so every gradient contribution from
+// them is zero.
+//
+// Ld names how a per-layer kernel loads its operands, and with it the core it runs on.
+// The instantiated set (lyr_run's NCF_LAUNCH_LD picks from it, nothing else is built):
+//   lyr_fwd_kernel, lyr_bwd_data_kernel, lyr_bwd_w_kernel <FIRST, LD> for FIRST in
+//   {true, false} and LD in {Scalar, ScalarDrop, Vec4}; bwd_w_body<false, Vec4, TB> for
+//   lyr_bwd_w_multi_kernel<TB>, TB in {64, 128}.
 #include <cstring>
 
 #include "ncf_common.h"
+#include "ncf_gemm.h"
 #include "ncf_layered.h"
 
 namespace ncf {
 namespace {
 
-constexpr int GBM = 64, GBN = 64, GBK = 16, GNT = 256, GPAD = 4;
+//   Scalar      any factor_num: one element per load, the f32 core
+//   ScalarDrop  Scalar with the dropout mask of the layer's input applied in the loaders
+//               (training steps with lay.dropout > 0 take it whatever factor_num is)
+//   Vec4        factor_num % 4 == 0: 16-byte loads, gemm_tile (the data gradient: the
+//               f32 core, see lyr_bwd_data_kernel)
+enum class Ld { Scalar, ScalarDrop, Vec4 };
 
 struct Sel {
     int64_t base, nloc;
@@ -136,479 +148,13 @@ __device__ __forceinline__ void row_ids(const LyrArgs& a, const Sel& s, int64_t 
     }
 }
 
-// Lane -> tile-element maps.  KC: the operand is contiguous along K (16 lanes
-// per row, 4 passes of 16 rows); otherwise contiguous along M/N (64 lanes per
-// k, 4 passes of 4 k).
-template <bool KC>
-__device__ __forceinline__ int map_mn(int t, int p) { return KC ? (t >> 4) + 16 * p : (t & 63); }
-template <bool KC>
-__device__ __forceinline__ int map_k(int t, int p) { return KC ? (t & 15) : (t >> 6) + 4 * p; }
-
-// Store-time hook on the A operand (sa(value) once per loaded element, when it is
-// written to LDS -- the load has landed by then, so no extra wait): the weight
-// gradient sums dY's columns through it for db_k.
-struct NoHook {
-    template <class T>
-    __device__ __forceinline__ void operator()(const T&) const {}
-};
-
-// C[mb..mb+32) x [nb..nb+32) for this wave: acc[ti][tj] reg r at
-// row 16*ti + 4*(l>>4) + r, col 16*tj + (l&15).
-template <bool AKC, bool BKC, class GA, class GB, class EP, class SA = NoHook>
-__device__ __forceinline__ void gemm_block(int64_t m0, int64_t n0, int64_t kbeg, int64_t kend, GA ga, GB gb,
-                                           EP ep, SA sa = SA{}) {
-    __shared__ float As[2][GBK][GBM + GPAD];
-    __shared__ float Bs[2][GBK][GBN + GPAD];
-    const int t = threadIdx.x, l = t & 63, w = t >> 6;
-    const int wm = (w >> 1) * 32, wn = (w & 1) * 32;
-    float ra[4], rb[4];
-    auto load = [&](int64_t k0) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) ra[p] = ga(map_mn<AKC>(t, p), k0 + map_k<AKC>(t, p));
-#pragma unroll
-        for (int p = 0; p < 4; ++p) rb[p] = gb(k0 + map_k<BKC>(t, p), map_mn<BKC>(t, p));
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) sa(ra[p]);
-#pragma unroll
-        for (int p = 0; p < 4; ++p) As[buf][map_k<AKC>(t, p)][map_mn<AKC>(t, p)] = ra[p];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) Bs[buf][map_k<BKC>(t, p)][map_mn<BKC>(t, p)] = rb[p];
-    };
-    f4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-    load(kbeg);
-    store(0);
-    __syncthreads();
-    int buf = 0;
-    for (int64_t k0 = kbeg; k0 < kend; k0 += GBK) {
-        const bool more = k0 + GBK < kend;
-        if (more) load(k0 + GBK);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int kk = 4 * s + (l >> 4);
-            const float a0 = As[buf][kk][wm + (l & 15)], a1 = As[buf][kk][wm + 16 + (l & 15)];
-            const float b0 = Bs[buf][kk][wn + (l & 15)], b1 = Bs[buf][kk][wn + 16 + (l & 15)];
-            acc[0][0] = MFMA4(a0, b0, acc[0][0]);
-            acc[0][1] = MFMA4(a0, b1, acc[0][1]);
-            acc[1][0] = MFMA4(a1, b0, acc[1][0]);
-            acc[1][1] = MFMA4(a1, b1, acc[1][1]);
-        }
-        if (more) store(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
-    (void)m0;
-    (void)n0;
-    ep(acc, wm, wn, l);
-}
-
-// Same tile and MFMA schedule with one 16-byte operand load per thread per K step:
-// ga4 / gb4 return four elements along the operand's contiguous dimension (KC: K,
-// else M/N), which must be a multiple of 4 with 16-byte aligned rows (factor_num
-// % 4 == 0).  KC tile [64][16]: thread t loads row t / 4, k 4 (t % 4) .. + 3;
-// otherwise [16][64]: k t / 16, columns 4 (t % 16) .. + 3 (one LDS f4 store).
-template <bool AKC, bool BKC, class GA, class GB, class EP, class SA = NoHook>
-__device__ __forceinline__ void gemm_block_v(int64_t kbeg, int64_t kend, GA ga4, GB gb4, EP ep, SA sa = SA{}) {
-    __shared__ __attribute__((aligned(16))) float As[2][GBK][GBM + GPAD];
-    __shared__ __attribute__((aligned(16))) float Bs[2][GBK][GBN + GPAD];
-    const int t = threadIdx.x, l = t & 63, w = t >> 6;
-    const int wm = (w >> 1) * 32, wn = (w & 1) * 32;
-    const int a_mn = AKC ? (t >> 2) : 4 * (t & 15), a_k = AKC ? 4 * (t & 3) : (t >> 4);
-    const int b_mn = BKC ? (t >> 2) : 4 * (t & 15), b_k = BKC ? 4 * (t & 3) : (t >> 4);
-    f4 ra, rb;
-    auto load = [&](int64_t k0) {
-        ra = ga4(a_mn, k0 + a_k);
-        rb = gb4(k0 + b_k, b_mn);
-    };
-    auto store = [&](int buf) {
-        sa(ra);
-        if constexpr (AKC) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) As[buf][a_k + i][a_mn] = lane_get(ra, i);
-        } else {
-            *reinterpret_cast<f4*>(&As[buf][a_k][a_mn]) = ra;
-        }
-        if constexpr (BKC) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) Bs[buf][b_k + i][b_mn] = lane_get(rb, i);
-        } else {
-            *reinterpret_cast<f4*>(&Bs[buf][b_k][b_mn]) = rb;
-        }
-    };
-    f4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-    load(kbeg);
-    store(0);
-    __syncthreads();
-    int buf = 0;
-    for (int64_t k0 = kbeg; k0 < kend; k0 += GBK) {
-        const bool more = k0 + GBK < kend;
-        if (more) load(k0 + GBK);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int kk = 4 * s + (l >> 4);
-            const float a0 = As[buf][kk][wm + (l & 15)], a1 = As[buf][kk][wm + 16 + (l & 15)];
-            const float b0 = Bs[buf][kk][wn + (l & 15)], b1 = Bs[buf][kk][wn + 16 + (l & 15)];
-            acc[0][0] = MFMA4(a0, b0, acc[0][0]);
-            acc[0][1] = MFMA4(a0, b1, acc[0][1]);
-            acc[1][0] = MFMA4(a1, b0, acc[1][0]);
-            acc[1][1] = MFMA4(a1, b1, acc[1][1]);
-        }
-        if (more) store(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
-    ep(acc, wm, wn, l);
-}
-
-// ---------------------------------------------------------------------------
-// fp32 GEMM on the bf16 matrix cores (three-plane split, six products).
-//
-// gfx950 runs v_mfma_f32_16x16x4_f32 at 1/16 of the bf16 rate and has no xf32.
-// Every fp32 operand element is split exactly into three bf16 planes by
-// round-to-nearest, x = h + m + l (h = bf16(x), m = bf16(x - h), l = x - h - m; each
-// remainder is exact in fp32 and the last fits bf16, so the sum is exact), and
-//   x * y ~= h h' + (h m' + m h') + (h l' + m m' + l h')
-// drops only m l', l m', l l': |m| <= 2^-8 |x|, |l| <= 2^-16 |x|, so each is
-// <= 2^-24 |x y| and, the residuals being signed, unbiased -- about one fp32
-// rounding per product (a truncating split leaves 8x larger, same-sign terms:
-// max 4.7e-7 against 5.9e-8 relative over 2M random pairs).
-// Accumulated in fp32 by v_mfma_f32_16x16x32_bf16 (exact bf16 x bf16 products).
-// Per K = 32: 6 bf16 MFMAs of 16 cycles against 8 f32 MFMAs of 32.
-//
-// gemm_block_x6s keeps gemm_block_v's contract (64 x 64 block tile, 4 waves of 32 x 32,
-// the same loaders, store hook and accumulator layout -- C/D of the bf16 16x16x32
-// MFMA is the f32 16x16x4 map), with K in steps of 32 through double-buffered LDS.
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int XBK = 32;
-
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float bitsf(uint32_t u) { return __builtin_bit_cast(float, u); }
-// (a, b) -> packed bf16 pair, round to nearest even (v_cvt_pk_bf16_f32), a in the low half
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-    const f2_t v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-// (x0, x1) -> three packed bf16 pairs (x0 in the low half): h, m, l with x = h + m + l
-__device__ __forceinline__ void split3(float x0, float x1, uint32_t& h, uint32_t& m, uint32_t& l) {
-    h = pk_bf16(x0, x1);
-    const float r0 = x0 - bitsf(h << 16), r1 = x1 - bitsf(h & 0xffff0000u);
-    m = pk_bf16(r0, r1);
-    const float s0 = r0 - bitsf(m << 16), s1 = r1 - bitsf(m & 0xffff0000u);
-    l = pk_bf16(s0, s1);
-}
-
-// B-operand loaders take (k, mn): adapt to the (mn, k) form above
-template <class G>
-struct X6Swap {
-    G g;
-    __device__ __forceinline__ f4 operator()(int mn, int64_t k) const { return g(k, mn); }
-};
-
-// The split happens in registers: the LDS holds the fp32 tiles ([mn][k], 32 k per row,
-// 4-float chunks XOR-swizzled by (r ^ r >> 3) & 7: conflict-free ds_read_b128 operand
-// reads and 16-byte stores, 2-way dword stores), 32 KB per block; each wave reads its
-// fragments (two ds_read_b128 per 16-row tile) and splits them before its MFMAs.
-__device__ __forceinline__ int x6s_addr(int r, int k) { return r * XBK + 4 * ((k >> 2) ^ ((r ^ (r >> 3)) & 7)) + (k & 3); }
-
-template <bool KC, class G>
-__device__ __forceinline__ void x6s_load(G g, int64_t k0, int t, f4 (&v)[2]) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int q = t + 256 * h;
-        v[h] = KC ? g(q >> 3, k0 + 4 * (q & 7)) : g(4 * (q & 15), k0 + (q >> 4));
-    }
-}
-template <bool KC>
-__device__ __forceinline__ void x6s_store(float* S, int t, const f4 (&v)[2]) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int q = t + 256 * h;
-        if constexpr (KC) {
-            *reinterpret_cast<f4*>(S + x6s_addr(q >> 3, 4 * (q & 7))) = v[h];
-        } else {
-            const int k = q >> 4, mn = 4 * (q & 15);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) S[x6s_addr(mn + i, k)] = lane_get(v[h], i);
-        }
-    }
-}
-// lane l's 8 k of row r (k 8 (l >> 4) .. + 7) -> the three bf16 planes of its fragment
-__device__ __forceinline__ void x6s_frag(const float* S, int r, int l, bf16x8 (&f)[3]) {
-    const int k = 8 * (l >> 4);
-    const f4 x = *reinterpret_cast<const f4*>(S + x6s_addr(r, k));
-    const f4 y = *reinterpret_cast<const f4*>(S + x6s_addr(r, k + 4));
-    uint4 h, m, lo;
-    split3(x.x, x.y, h.x, m.x, lo.x);
-    split3(x.z, x.w, h.y, m.y, lo.y);
-    split3(y.x, y.y, h.z, m.z, lo.z);
-    split3(y.z, y.w, h.w, m.w, lo.w);
-    f[0] = __builtin_bit_cast(bf16x8, h);
-    f[1] = __builtin_bit_cast(bf16x8, m);
-    f[2] = __builtin_bit_cast(bf16x8, lo);
-}
-
-template <bool AKC, bool BKC, class GA, class GB, class EP, class SA = NoHook>
-__device__ __forceinline__ void gemm_block_x6s(int64_t kbeg, int64_t kend, GA ga4, GB gb4, EP ep, SA sa = SA{}) {
-    __shared__ __attribute__((aligned(16))) float As[2][64 * XBK];
-    __shared__ __attribute__((aligned(16))) float Bs[2][64 * XBK];
-    const int t = threadIdx.x, l = t & 63, w = t >> 6;
-    const int wm = (w >> 1) * 32, wn = (w & 1) * 32;
-    const X6Swap<GB> gbs{gb4};
-    f4 ra[2], rb[2];
-    auto load = [&](int64_t k0) {
-        x6s_load<AKC>(ga4, k0, t, ra);
-        x6s_load<BKC>(gbs, k0, t, rb);
-    };
-    auto store = [&](int buf) {
-        sa(ra[0]);
-        sa(ra[1]);
-        x6s_store<AKC>(As[buf], t, ra);
-        x6s_store<BKC>(Bs[buf], t, rb);
-    };
-    f4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-    load(kbeg);
-    store(0);
-    __syncthreads();
-    int buf = 0;
-    for (int64_t k0 = kbeg; k0 < kend; k0 += XBK) {
-        const bool more = k0 + XBK < kend;
-        if (more) load(k0 + XBK);
-        bf16x8 fa[2][3], fb[2][3];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            x6s_frag(As[buf], wm + 16 * i + (l & 15), l, fa[i]);
-            x6s_frag(Bs[buf], wn + 16 * i + (l & 15), l, fb[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                f4 c = acc[i][j];
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][2], fb[j][0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][1], fb[j][1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fb[j][2], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][1], fb[j][0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fb[j][1], c, 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fb[j][0], c, 0, 0, 0);
-            }
-        if (more) store(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
-    ep(acc, wm, wn, l);
-}
-
-// gemm_block_x6w: the split core on a 128 x 128 block tile, each of the 4 waves a 64 x 64
-// quadrant (4 x 4 MFMA tiles).  The x6s core's waves own 32 x 32 quadrants: per K step a
-// wave splits 4 fragments (three bf16 planes each, ~40 VALU per fragment) for 24 MFMAs,
-// and a wave64 VALU instruction occupies the SIMD 4 cycles -- ~960 VALU cycles against
-// 384 MFMA cycles, so the split sets the time (SQ: 10 VALU per MFMA instruction in the
-// weight-gradient launch, MFMA busy 0.21).  Here a wave splits 8 fragments for 96 MFMAs.
-// Same planes, products, product order and K order per output element as x6s (the
-// outputs are bitwise the same for the same K range).  LDS: 2 x (128 + 128) x 32 fp32
-// = 64 KB, dynamic (X6W_LDS bytes; launchers set the attribute).  The epilogue gets
-// acc[4][4] and the wave's quadrant origin (wm, wn) in {0, 64}.
-constexpr int X6W_TB = 128;
-constexpr int X6W_LDS = 2 * 2 * X6W_TB * XBK * 4;
-
-template <bool KC, int TB, class G>
-__device__ __forceinline__ void x6w_load(G g, int64_t k0, int t, f4 (&v)[TB / 32]) {
-#pragma unroll
-    for (int h = 0; h < TB / 32; ++h) {
-        const int q = t + 256 * h;
-        v[h] = KC ? g(q >> 3, k0 + 4 * (q & 7)) : g(4 * (q % (TB / 4)), k0 + q / (TB / 4));
-    }
-}
-// (A register-transposed form for !KC -- four consecutive k rows per thread stored as f4
-// along k -- removed the weight-gradient launch's 17M LDS bank-conflict cycles but ran
-// 164.5 -> 194.8 us: profiles/r06_evidence/gemm_tile_ab/.)
-template <bool KC, int TB>
-__device__ __forceinline__ void x6w_store(float* S, int t, const f4 (&v)[TB / 32]) {
-#pragma unroll
-    for (int h = 0; h < TB / 32; ++h) {
-        const int q = t + 256 * h;
-        if constexpr (KC) {
-            *reinterpret_cast<f4*>(S + x6s_addr(q >> 3, 4 * (q & 7))) = v[h];
-        } else {
-            const int k = q / (TB / 4), mn = 4 * (q % (TB / 4));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) S[x6s_addr(mn + i, k)] = lane_get(v[h], i);
-        }
-    }
-}
-
-template <bool AKC, bool BKC, class GA, class GB, class EP, class SA = NoHook>
-__device__ __forceinline__ void gemm_block_x6w(int64_t kbeg, int64_t kend, GA ga4, GB gb4, EP ep, SA sa = SA{}) {
-    constexpr int TB = X6W_TB, NH = TB / 32;
-    extern __shared__ __attribute__((aligned(16))) float x6w_sm[];
-    float* As = x6w_sm;                  // [2][TB * XBK]
-    float* Bs = x6w_sm + 2 * TB * XBK;   // [2][TB * XBK]
-    const int t = threadIdx.x, l = t & 63, w = t >> 6;
-    const int wm = (w >> 1) * 64, wn = (w & 1) * 64;
-    const X6Swap<GB> gbs{gb4};
-    f4 ra[NH], rb[NH];
-    auto load = [&](int64_t k0) {
-        x6w_load<AKC, TB>(ga4, k0, t, ra);
-        x6w_load<BKC, TB>(gbs, k0, t, rb);
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-        for (int h = 0; h < NH; ++h) sa(ra[h]);
-        x6w_store<AKC, TB>(As + buf * TB * XBK, t, ra);
-        x6w_store<BKC, TB>(Bs + buf * TB * XBK, t, rb);
-    };
-    f4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-    load(kbeg);
-    store(0);
-    __syncthreads();
-    int buf = 0;
-    for (int64_t k0 = kbeg; k0 < kend; k0 += XBK) {
-        const bool more = k0 + XBK < kend;
-        if (more) load(k0 + XBK);
-        const float* Ab = As + buf * TB * XBK;
-        const float* Bb = Bs + buf * TB * XBK;
-        bf16x8 fa[4][3];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) x6s_frag(Ab, wm + 16 * i + (l & 15), l, fa[i]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            bf16x8 fb[3];
-            x6s_frag(Bb, wn + 16 * j + (l & 15), l, fb);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                f4 c = acc[i][j];
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][2], fb[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][1], fb[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fb[2], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][1], fb[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fb[1], c, 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fb[0], c, 0, 0, 0);
-            }
-        }
-        if (more) store(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
-    ep(acc, wm, wn, l);
-}
-
-// gemm_block_x6b: the x6s core (64 x 64 block tile, 4 waves of 32 x 32) with the B
-// operand already split: bimg is the block's first 16-column group of a fragment-major
-// image (lyr_wc_prep_kernel's W0 images: per 16-column group ngs bytes, per K step of 32
-// three planes x 64 lanes x 16 B), read straight from memory (L2-resident, 1.5 MB per
-// image) one K step ahead.  Only A passes through LDS and the split, so a wave splits 2
-// fragments per 24 MFMAs instead of 4 (the weight operand is split once per step instead
-// of once per block).  Same planes, products and K order per element as x6s.
-template <bool AKC, class GA, class EP>
-__device__ __forceinline__ void gemm_block_x6b(int64_t kbeg, int64_t kend, GA ga4, const char* __restrict__ bimg,
-                                               int64_t ngs, EP ep) {
-    __shared__ __attribute__((aligned(16))) float As[2][64 * XBK];
-    const int t = threadIdx.x, l = t & 63, w = t >> 6;
-    const int wm = (w >> 1) * 32, wn = (w & 1) * 32;
-    f4 ra[2];
-    bf16x8 fb[2][3], fn[2][3];
-    auto load_b = [&](int64_t k0, bf16x8 (&f)[2][3]) {
-        const char* p = bimg + (k0 / XBK) * 3072 + l * 16;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                f[j][q] = *reinterpret_cast<const bf16x8*>(p + (int64_t)(wn / 16 + j) * ngs + q * 1024);
-    };
-    f4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-    x6s_load<AKC>(ga4, kbeg, t, ra);
-    load_b(kbeg, fb);
-    x6s_store<AKC>(As[0], t, ra);
-    __syncthreads();
-    int buf = 0;
-    for (int64_t k0 = kbeg; k0 < kend; k0 += XBK) {
-        const bool more = k0 + XBK < kend;
-        if (more) {
-            x6s_load<AKC>(ga4, k0 + XBK, t, ra);
-            load_b(k0 + XBK, fn);
-        }
-        bf16x8 fa[2][3];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) x6s_frag(As[buf], wm + 16 * i + (l & 15), l, fa[i]);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                f4 c = acc[i][j];
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][2], fb[j][0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][1], fb[j][1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fb[j][2], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][1], fb[j][0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fb[j][1], c, 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fb[j][0], c, 0, 0, 0);
-            }
-        if (more) {
-            x6s_store<AKC>(As[buf ^ 1], t, ra);
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int q = 0; q < 3; ++q) fb[j][q] = fn[j][q];
-        }
-        __syncthreads();
-        buf ^= 1;
-    }
-    ep(acc, wm, wn, l);
-}
-
-// The GEMM core of the layered kernels' 16-byte loader path: the bf16 split core, or
-// (-DNCF_GEMM_F32, the A/B library variant) the f32-MFMA core.  (A variant that split
-// once per block into three bf16 plane images in LDS -- 48 KB per block, 3 blocks per
-// CU -- measured slower: stress 1304 against 1093 us per step.)
-template <bool AKC, bool BKC, class GA, class GB, class EP, class SA = NoHook>
-__device__ __forceinline__ void gemm_block_vx(int64_t kbeg, int64_t kend, GA ga4, GB gb4, EP ep, SA sa = SA{}) {
-#if defined(NCF_GEMM_F32)
-    gemm_block_v<AKC, BKC>(kbeg, kend, ga4, gb4, ep, sa);
-#else
-    gemm_block_x6s<AKC, BKC>(kbeg, kend, ga4, gb4, ep, sa);
-#endif
-}
-
-// TB = 64: gemm_block_vx; TB = X6W_TB: the 128 x 128 split core (dynamic LDS X6W_LDS)
-template <int TB, bool AKC, bool BKC, class GA, class GB, class EP, class SA = NoHook>
-__device__ __forceinline__ void gemm_tile(int64_t kbeg, int64_t kend, GA ga4, GB gb4, EP ep, SA sa = SA{}) {
-    static_assert(TB == 64 || TB == X6W_TB, "block tile");
-    if constexpr (TB == X6W_TB)
-        gemm_block_x6w<AKC, BKC>(kbeg, kend, ga4, gb4, ep, sa);
-    else
-        gemm_block_vx<AKC, BKC>(kbeg, kend, ga4, gb4, ep, sa);
-}
-
-__device__ __forceinline__ f4 ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
-__device__ __forceinline__ f4 zero4() { return f4{0.f, 0.f, 0.f, 0.f}; }
-
 // ---------------------------------------------------------------------------
 // Forward layer k: H_{k+1}[m][n] = ReLU(sum_c A[m][c] W_k[n][c] + b_k[n]).
 // grid (ceil(R/64), ceil(N/64)).
-template <bool FIRST, bool DROP, bool VEC>
+template <bool FIRST, Ld LD>
 __global__ __launch_bounds__(GNT) void lyr_fwd_kernel(LyrArgs a, int k, const float* __restrict__ Ain,
                                                       float* __restrict__ Hout, int64_t R) {
+    constexpr bool DROP = LD == Ld::ScalarDrop;
     __shared__ int su[GBM], si[GBM];
     const Sel s = select_rows(a);
     const ncf_layout& lay = a.lay;
@@ -629,61 +175,47 @@ __global__ __launch_bounds__(GNT) void lyr_fwd_kernel(LyrArgs a, int k, const fl
         si[threadIdx.x] = it < 0 ? 0 : it;
     }
     if (FIRST) __syncthreads();
-    const Drop dr = DROP ? drop_of(a) : Drop{false, 0, 0, 0, 1.f};
-    auto ga = [&](int r, int64_t c) -> float {
-        const int64_t m = m0 + r;
-        if (m >= R || c >= K) return 0.f;
-        float v;
-        if constexpr (FIRST) {
-            v = c < DM ? prm[lay.um + (int64_t)su[r] * DM + c] : prm[lay.im + (int64_t)si[r] * DM + (c - DM)];
-        } else {
-            v = Ain[m * K + c];
-        }
-        if constexpr (DROP) v *= drop_mul(dr, k, s.base + m, (int)c);
-        return v;
+    auto ep = [&](int c) {
+        const int n = n0 + c;
+        const float bn = n < N ? bias[n] : 0.f;
+        return [&, n, bn](int r, float v) {
+            const int64_t m = m0 + r;
+            if (n < N && m < R) Hout[m * N + n] = fmaxf(v + bn, 0.f);
+        };
     };
-    auto gb = [&](int64_t c, int n) -> float {
-        const int nn = n0 + n;
-        return (nn < N && c < K) ? W[(int64_t)nn * K + c] : 0.f;
-    };
-    auto ep = [&](f4 (&acc)[2][2], int wm, int wn, int l) {
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) {
-                const int n = n0 + wn + 16 * tj + (l & 15);
-                if (n >= N) continue;
-                const float bn = bias[n];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int64_t m = m0 + wm + 16 * ti + 4 * (l >> 4) + r;
-                    if (m < R) Hout[m * N + n] = fmaxf(lane_get(acc[ti][tj], r) + bn, 0.f);
-                }
-            }
-    };
-    if constexpr (VEC) {
+    if constexpr (LD == Ld::Vec4) {
         auto ga4 = [&](int r, int64_t c) -> f4 {
             const int64_t m = m0 + r;
             if (m >= R || c >= K) return zero4();
-            f4 v;
-            if constexpr (FIRST) {
-                v = c < DM ? ld4(prm + lay.um + (int64_t)su[r] * DM + c) : ld4(prm + lay.im + (int64_t)si[r] * DM + (c - DM));
-            } else {
-                v = ld4(Ain + m * K + c);
-            }
-            if constexpr (DROP) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] *= drop_mul(dr, k, s.base + m, (int)c + i);
-            }
-            return v;
+            if constexpr (FIRST)
+                return c < DM ? ld4(prm + lay.um + (int64_t)su[r] * DM + c) : ld4(prm + lay.im + (int64_t)si[r] * DM + (c - DM));
+            else
+                return ld4(Ain + m * K + c);
         };
         auto gb4 = [&](int64_t c, int n) -> f4 {
             const int nn = n0 + n;
             return (nn < N && c < K) ? ld4(W + (int64_t)nn * K + c) : zero4();
         };
-        gemm_block_vx<true, true>(0, K, ga4, gb4, ep);
+        gemm_tile<64, true, true>(0, K, ga4, gb4, ep);
     } else {
-        gemm_block<true, true>(m0, n0, 0, K, ga, gb, ep);
+        const Drop dr = DROP ? drop_of(a) : Drop{false, 0, 0, 0, 1.f};
+        auto ga = [&](int r, int64_t c) -> float {
+            const int64_t m = m0 + r;
+            if (m >= R || c >= K) return 0.f;
+            float v;
+            if constexpr (FIRST) {
+                v = c < DM ? prm[lay.um + (int64_t)su[r] * DM + c] : prm[lay.im + (int64_t)si[r] * DM + (c - DM)];
+            } else {
+                v = Ain[m * K + c];
+            }
+            if constexpr (DROP) v *= drop_mul(dr, k, s.base + m, (int)c);
+            return v;
+        };
+        auto gb = [&](int64_t c, int n) -> float {
+            const int nn = n0 + n;
+            return (nn < N && c < K) ? W[(int64_t)nn * K + c] : 0.f;
+        };
+        gemm_block_f32<F32Scalar, true, true>(0, K, ga, gb, ep);
     }
 }
 
@@ -692,10 +224,11 @@ __global__ __launch_bounds__(GNT) void lyr_fwd_kernel(LyrArgs a, int k, const fl
 //   k > 0: dY_{k-1}[m][n] = C * [H_k[m][n] > 0]
 //   k = 0: scatter-add C into grad Um[u_m] (n < dm) / Im[i_m] (n >= dm)
 // grid (ceil(R/64), ceil(s_k/64)).
-template <bool FIRST, bool DROP, bool VEC>
+template <bool FIRST, Ld LD>
 __global__ __launch_bounds__(GNT) void lyr_bwd_data_kernel(LyrArgs a, int k, const float* __restrict__ D,
                                                            const float* __restrict__ Hk, float* __restrict__ Dout,
                                                            int64_t R) {
+    constexpr bool DROP = LD == Ld::ScalarDrop;
     __shared__ int su[GBM], si[GBM];
     const Sel s = select_rows(a);
     const ncf_layout& lay = a.lay;
@@ -714,41 +247,20 @@ __global__ __launch_bounds__(GNT) void lyr_bwd_data_kernel(LyrArgs a, int k, con
     }
     if (FIRST) __syncthreads();
     const Drop dr = DROP ? drop_of(a) : Drop{false, 0, 0, 0, 1.f};
-    auto ga = [&](int r, int64_t j) -> float {
-        const int64_t m = m0 + r;
-        return (m < R && j < J) ? D[m * J + j] : 0.f;
+    auto ep = [&](int rr, int c, float v) {
+        const int n = n0 + c;
+        const int64_t m = m0 + rr;
+        if (n >= N || m >= R) return;
+        if constexpr (DROP) v *= drop_mul(dr, k, s.base + m, n);  // through layer k's input dropout
+        if constexpr (FIRST) {
+            const int id = n < DM ? su[rr] : si[rr];
+            if (id >= 0)
+                atomicAdd(a.grads + (n < DM ? lay.um + (int64_t)id * DM + n : lay.im + (int64_t)id * DM + (n - DM)), v);
+        } else {
+            Dout[m * N + n] = Hk[m * N + n] > 0.f ? v : 0.f;
+        }
     };
-    auto gb = [&](int64_t j, int n) -> float {
-        const int nn = n0 + n;
-        return (j < J && nn < N) ? W[j * N + nn] : 0.f;
-    };
-    auto ep = [&](f4 (&acc)[2][2], int wm, int wn, int l) {
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) {
-                const int n = n0 + wn + 16 * tj + (l & 15);
-                if (n >= N) continue;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int rr = wm + 16 * ti + 4 * (l >> 4) + r;
-                    const int64_t m = m0 + rr;
-                    if (m >= R) continue;
-                    float v = lane_get(acc[ti][tj], r);
-                    if constexpr (DROP) v *= drop_mul(dr, k, s.base + m, n);  // through layer k's input dropout
-                    if constexpr (FIRST) {
-                        const int id = n < DM ? su[rr] : si[rr];
-                        if (id >= 0)
-                            atomicAdd(a.grads + (n < DM ? lay.um + (int64_t)id * DM + n
-                                                        : lay.im + (int64_t)id * DM + (n - DM)),
-                                      v);
-                    } else {
-                        Dout[m * N + n] = Hk[m * N + n] > 0.f ? v : 0.f;
-                    }
-                }
-            }
-    };
-    if constexpr (VEC) {
+    if constexpr (LD == Ld::Vec4) {
         auto ga4 = [&](int r, int64_t j) -> f4 {
             const int64_t m = m0 + r;
             return (m < R && j < J) ? ld4(D + m * J + j) : zero4();
@@ -760,9 +272,17 @@ __global__ __launch_bounds__(GNT) void lyr_bwd_data_kernel(LyrArgs a, int k, con
         // K = J <= 256 here (2-8 K steps of 32): the masked epilogue dominates and the
         // f32 core's occupancy (8 waves / SIMD against 3) wins -- stress 88.8 against
         // 95.4 us per launch with the split core (profiles/r03x6/stress_kernel_stats_*.csv)
-        gemm_block_v<true, false>(0, J, ga4, gb4, ep);
+        gemm_block_f32<F32Vec4, true, false>(0, J, ga4, gb4, ep);
     } else {
-        gemm_block<true, false>(m0, n0, 0, J, ga, gb, ep);
+        auto ga = [&](int r, int64_t j) -> float {
+            const int64_t m = m0 + r;
+            return (m < R && j < J) ? D[m * J + j] : 0.f;
+        };
+        auto gb = [&](int64_t j, int n) -> float {
+            const int nn = n0 + n;
+            return (j < J && nn < N) ? W[j * N + nn] : 0.f;
+        };
+        gemm_block_f32<F32Scalar, true, false>(0, J, ga, gb, ep);
     }
 }
 
@@ -772,13 +292,14 @@ __global__ __launch_bounds__(GNT) void lyr_bwd_data_kernel(LyrArgs a, int k, con
 //   db_k[j]    += sum_m dY_k[m][j]             (the extra column c = s_k of ones)
 // into the slab (tower partials, reduced by ncf_reduce_slab).
 // grid (ceil(J/64), ceil((s_k+1)/64), splits).
-template <bool FIRST, bool DROP, bool VEC, int TB = 64>
+template <bool FIRST, Ld LD, int TB = 64>
 __device__ __forceinline__ void bwd_w_body(const LyrArgs& a, int k, const float* __restrict__ D,
                                            const float* __restrict__ Ain, int64_t R, int64_t chunk, int bx, int by,
                                            int bz) {
+    constexpr bool DROP = LD == Ld::ScalarDrop, VEC = LD == Ld::Vec4;
     static_assert(TB == 64 || (VEC && !FIRST), "the 128-tile core: 16-byte loaders, layers k >= 1");
-    constexpr int NT = TB / 32;
-    __shared__ int su[FIRST ? GBK * 64 : 1], si[FIRST ? GBK * 64 : 1];  // ids of up to 1024 rows of the chunk (FIRST)
+    constexpr int SUB = GBK * 64;  // FIRST: rows per pass, their ids staged in LDS
+    __shared__ int su[FIRST ? SUB : 1], si[FIRST ? SUB : 1];
     const Sel s = select_rows(a);
     const ncf_layout& lay = a.lay;
     const int DM = lay.factor_num << (lay.num_layers - 1);
@@ -811,98 +332,65 @@ __device__ __forceinline__ void bwd_w_body(const LyrArgs& a, int k, const float*
     auto sa1 = [&](const float& v) {
         if (dbt) db1 += v;
     };
-    auto ep = [&](f4 (&acc)[NT][NT], int wm, int wn, int l) {
-#pragma unroll
-        for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < NT; ++tj) {
-                const int c = c0 + wn + 16 * tj + (l & 15);
-                if (c >= K) continue;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int j = j0 + wm + 16 * ti + 4 * (l >> 4) + r;
-                    if (j >= J) continue;
-                    atomicAdd(slab + (lay.w[k] - tb) + (int64_t)j * K + c, lane_get(acc[ti][tj], r));
-                }
-            }
+    auto ep = [&](int jr, int cr, float v) {
+        const int j = j0 + jr, c = c0 + cr;
+        if (j < J && c < K) atomicAdd(slab + (lay.w[k] - tb) + (int64_t)j * K + c, v);
     };
-    auto ga = [&](int jr, int64_t m) -> float {
-        const int j = j0 + jr;
-        return (m < r1 && j < J) ? D[m * J + j] : 0.f;
+    // rows [q0, q1) of the chunk: A = dY_k^T, B = the layer's input (FIRST: gathered
+    // through the ids staged for q0 ..)
+    auto gemm_rows = [&](int64_t q0, int64_t q1) {
+        if constexpr (VEC) {
+            auto ga4 = [&](int jr, int64_t m) -> f4 {
+                const int j = j0 + jr;
+                return (m < q1 && j < J) ? ld4(D + m * J + j) : zero4();
+            };
+            auto gb4 = [&](int64_t m, int cr) -> f4 {
+                const int c = c0 + cr;
+                if (m >= q1 || c >= K) return zero4();
+                if constexpr (FIRST) {
+                    const int e = (int)(m - q0);
+                    return c < DM ? ld4(prm + lay.um + (int64_t)su[e] * DM + c)
+                                  : ld4(prm + lay.im + (int64_t)si[e] * DM + (c - DM));
+                } else {
+                    return ld4(Ain + m * K + c);
+                }
+            };
+            gemm_tile<TB, false, false>(q0, q1, ga4, gb4, ep, sa4);
+        } else {
+            auto ga = [&](int jr, int64_t m) -> float {
+                const int j = j0 + jr;
+                return (m < q1 && j < J) ? D[m * J + j] : 0.f;
+            };
+            auto gb = [&](int64_t m, int cr) -> float {
+                const int c = c0 + cr;
+                if (m >= q1 || c >= K) return 0.f;
+                float v;
+                if constexpr (FIRST) {
+                    const int e = (int)(m - q0);
+                    v = c < DM ? prm[lay.um + (int64_t)su[e] * DM + c] : prm[lay.im + (int64_t)si[e] * DM + (c - DM)];
+                } else {
+                    v = Ain[m * K + c];
+                }
+                if constexpr (DROP) v *= drop_mul(dr, k, s.base + m, c);
+                return v;
+            };
+            gemm_block_f32<F32Scalar, false, false>(q0, q1, ga, gb, ep, sa1);
+        }
     };
     if constexpr (FIRST) {
-        // rows processed in sub-chunks of 1024 with their ids staged in LDS
-        for (int64_t q0 = r0; q0 < r1; q0 += GBK * 64) {
-            const int64_t q1 = q0 + GBK * 64 < r1 ? q0 + GBK * 64 : r1;
+        for (int64_t q0 = r0; q0 < r1; q0 += SUB) {
             __syncthreads();
-            for (int e = threadIdx.x; e < GBK * 64; e += GNT) {
+            for (int e = threadIdx.x; e < SUB; e += GNT) {
                 int u, it;
                 row_ids(a, s, q0 + e, u, it);
                 su[e] = u < 0 ? 0 : u;
                 si[e] = it < 0 ? 0 : it;
             }
             __syncthreads();
-            auto gb = [&](int64_t m, int cr) -> float {
-                const int c = c0 + cr;
-                if (m >= q1 || c >= K) return 0.f;
-                const int e = (int)(m - q0);
-                float v = c < DM ? prm[lay.um + (int64_t)su[e] * DM + c] : prm[lay.im + (int64_t)si[e] * DM + (c - DM)];
-                if constexpr (DROP) v *= drop_mul(dr, k, s.base + m, c);
-                return v;
-            };
-            auto ga2 = [&](int jr, int64_t m) -> float {
-                const int j = j0 + jr;
-                return (m < q1 && j < J) ? D[m * J + j] : 0.f;
-            };
-            if constexpr (VEC) {
-                auto ga4 = [&](int jr, int64_t m) -> f4 {
-                    const int j = j0 + jr;
-                    return (m < q1 && j < J) ? ld4(D + m * J + j) : zero4();
-                };
-                auto gb4 = [&](int64_t m, int cr) -> f4 {
-                    const int c = c0 + cr;
-                    if (m >= q1 || c >= K) return zero4();
-                    const int e = (int)(m - q0);
-                    f4 v = c < DM ? ld4(prm + lay.um + (int64_t)su[e] * DM + c)
-                                  : ld4(prm + lay.im + (int64_t)si[e] * DM + (c - DM));
-                    if constexpr (DROP) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) v[i] *= drop_mul(dr, k, s.base + m, c + i);
-                    }
-                    return v;
-                };
-                gemm_block_vx<false, false>(q0, q1, ga4, gb4, ep, sa4);
-            } else {
-                gemm_block<false, false>(j0, c0, q0, q1, ga2, gb, ep, sa1);
-            }
+            gemm_rows(q0, q0 + SUB < r1 ? q0 + SUB : r1);
         }
     } else {
-        auto gb = [&](int64_t m, int cr) -> float {
-            const int c = c0 + cr;
-            if (m >= r1 || c >= K) return 0.f;
-            float v = Ain[m * K + c];
-            if constexpr (DROP) v *= drop_mul(dr, k, s.base + m, c);
-            return v;
-        };
-        if constexpr (VEC) {
-            auto ga4 = [&](int jr, int64_t m) -> f4 {
-                const int j = j0 + jr;
-                return (m < r1 && j < J) ? ld4(D + m * J + j) : zero4();
-            };
-            auto gb4 = [&](int64_t m, int cr) -> f4 {
-                const int c = c0 + cr;
-                if (m >= r1 || c >= K) return zero4();
-                f4 v = ld4(Ain + m * K + c);
-                if constexpr (DROP) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] *= drop_mul(dr, k, s.base + m, c + i);
-                }
-                return v;
-            };
-            gemm_tile<TB, false, false>(r0, r1, ga4, gb4, ep, sa4);
-        } else {
-            if constexpr (TB == 64) gemm_block<false, false>(j0, c0, r0, r1, ga, gb, ep, sa1);
-        }
+        gemm_rows(r0, r1);
     }
     if (dbt) {  // db_k: per-thread column sums -> LDS -> one atomic per column per block
         // A operand [TB / 4 rows of m][TB j] per load: VEC thread t holds j 4 (t % (TB / 4))
@@ -927,7 +415,7 @@ __device__ __forceinline__ void bwd_w_body(const LyrArgs& a, int k, const float*
     }
 }
 
-template <bool FIRST, bool DROP, bool VEC>
+template <bool FIRST, Ld LD>
 __global__ __launch_bounds__(GNT) void lyr_bwd_w_kernel(LyrArgs a, int k, const float* __restrict__ D,
                                                         const float* __restrict__ Ain, int64_t R, int64_t chunk) {
     // XCD-aware order (xcd_tile): the (j, column) tiles of one row chunk share an XCD,
@@ -937,7 +425,7 @@ __global__ __launch_bounds__(GNT) void lyr_bwd_w_kernel(LyrArgs a, int k, const 
     const int64_t q = nwg / 8, r = nwg % 8, x = orig % 8;
     const int64_t w = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + orig / 8;
     const int bz = (int)(w / per), rem = (int)(w % per);
-    bwd_w_body<FIRST, DROP, VEC>(a, k, D, Ain, R, chunk, rem % gridDim.x, rem / gridDim.x, bz);
+    bwd_w_body<FIRST, LD>(a, k, D, Ain, R, chunk, rem % gridDim.x, rem / gridDim.x, bz);
 }
 
 // The weight gradients of several layers k >= 1 in one launch (the step chain leaves
@@ -973,7 +461,7 @@ __global__ __launch_bounds__(GNT) void lyr_bwd_w_multi_kernel(LyrArgs a, BwMulti
         if (q < m.n && b >= m.start[q]) i = q;
     const int loc = b - m.start[i], per = m.gx[i] * m.gy[i];
     const int bz = loc / per, rem = loc - bz * per;
-    bwd_w_body<false, false, true, TB>(a, m.k[i], m.D[i], m.A[i], R, m.chunk[i], rem % m.gx[i], rem / m.gx[i], bz);
+    bwd_w_body<false, Ld::Vec4, TB>(a, m.k[i], m.D[i], m.A[i], R, m.chunk[i], rem % m.gx[i], rem / m.gx[i], bz);
 }
 
 // ---------------------------------------------------------------------------
@@ -990,7 +478,6 @@ __global__ __launch_bounds__(GNT) void lyr_proj_kernel(ncf_layout lay, const flo
                                                        float* __restrict__ P, int nbu, float* __restrict__ zp,
                                                        int64_t zn4, const char* __restrict__ bimg = nullptr) {
     if (zp != nullptr) zero_share(zp, zn4);
-    constexpr int NT = TB / 32;  // 16 x 16 tiles per wave side
     const int DM = lay.factor_num << (lay.num_layers - 1);
     const bool user = (int)blockIdx.x < nbu;
     const int64_t nrows = user ? lay.user_num : lay.item_num;
@@ -999,19 +486,10 @@ __global__ __launch_bounds__(GNT) void lyr_proj_kernel(ncf_layout lay, const flo
     const float* X = prm + (user ? lay.um : lay.im);
     const float* W = prm + lay.w[0] + (user ? 0 : DM);  // row stride 2 DM
     float* Pout = P + (user ? 0 : (int64_t)lay.user_num * DM);
-    auto ep = [&](f4 (&acc)[NT][NT], int wm, int wn, int l) {
-#pragma unroll
-        for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < NT; ++tj) {
-                const int n = n0 + wn + 16 * tj + (l & 15);
-                if (n >= DM) continue;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int64_t m = m0 + wm + 16 * ti + 4 * (l >> 4) + r;
-                    if (m < nrows) Pout[m * DM + n] = lane_get(acc[ti][tj], r);
-                }
-            }
+    auto ep = [&](int r, int c, float v) {
+        const int64_t m = m0 + r;
+        const int n = n0 + c;
+        if (m < nrows && n < DM) Pout[m * DM + n] = v;
     };
     auto ga4 = [&](int r, int64_t c) -> f4 {
         const int64_t m = m0 + r;
@@ -1045,7 +523,6 @@ template <int TB, bool BPRE = false>
 __global__ __launch_bounds__(GNT) void lyr_fact_dx_kernel(ncf_layout lay, const float* __restrict__ prm,
                                                           const float* __restrict__ grads, float* __restrict__ out,
                                                           int nbu, const char* __restrict__ bimg = nullptr) {
-    constexpr int NT = TB / 32;
     const int DM = lay.factor_num << (lay.num_layers - 1);
     const bool user = (int)blockIdx.x < nbu;
     const int64_t nrows = user ? lay.user_num : lay.item_num;
@@ -1054,19 +531,10 @@ __global__ __launch_bounds__(GNT) void lyr_fact_dx_kernel(ncf_layout lay, const 
     const float* G = grads + (user ? lay.um : lay.im);
     const float* W = prm + lay.w[0] + (user ? 0 : DM);  // W0[o][koff + i], row stride 2 DM
     float* O = out + (user ? 0 : (int64_t)lay.user_num * DM);
-    auto ep = [&](f4 (&acc)[NT][NT], int wm, int wn, int l) {
-#pragma unroll
-        for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < NT; ++tj) {
-                const int n = n0 + wn + 16 * tj + (l & 15);
-                if (n >= DM) continue;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int64_t m = m0 + wm + 16 * ti + 4 * (l >> 4) + r;
-                    if (m < nrows) O[m * DM + n] = lane_get(acc[ti][tj], r);
-                }
-            }
+    auto ep = [&](int r, int c, float v) {
+        const int64_t m = m0 + r;
+        const int n = n0 + c;
+        if (m < nrows && n < DM) O[m * DM + n] = v;
     };
     auto ga4 = [&](int r, int64_t k) -> f4 {  // G[m][o..o+3]
         const int64_t m = m0 + r;
@@ -1087,7 +555,6 @@ __global__ __launch_bounds__(GNT) void lyr_fact_dx_kernel(ncf_layout lay, const 
 
 template <int TB>
 __global__ __launch_bounds__(GNT) void lyr_fact_dw0_kernel(LyrArgs a, int zu, int64_t chunk) {
-    constexpr int NT = TB / 32;
     const ncf_layout& lay = a.lay;
     const int DM = lay.factor_num << (lay.num_layers - 1);
     const bool user = (int)blockIdx.z < zu;
@@ -1101,19 +568,9 @@ __global__ __launch_bounds__(GNT) void lyr_fact_dw0_kernel(LyrArgs a, int zu, in
     const int koff = user ? 0 : DM;
     float* slab = a.slab + (int64_t)(blockIdx.z % lyr_slab_rows(&lay)) * (lay.tower_len + 64) +
                   (lay.w[0] - lay.tower_begin);
-    auto ep = [&](f4 (&acc)[NT][NT], int wm, int wn, int l) {
-#pragma unroll
-        for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < NT; ++tj) {
-                const int c = c0 + wn + 16 * tj + (l & 15);
-                if (c >= DM) continue;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int o = o0 + wm + 16 * ti + 4 * (l >> 4) + r;
-                    if (o < DM) atomicAdd(slab + (int64_t)o * 2 * DM + koff + c, lane_get(acc[ti][tj], r));
-                }
-            }
+    auto ep = [&](int r, int cr, float v) {
+        const int o = o0 + r, c = c0 + cr;
+        if (o < DM && c < DM) atomicAdd(slab + (int64_t)o * 2 * DM + koff + c, v);
     };
     auto ga4 = [&](int jr, int64_t m) -> f4 {  // G[m][o .. o + 3]
         const int o = o0 + jr;
@@ -1698,6 +1155,19 @@ static void launch_scatter0(const LyrArgs& a, const float* D0, int64_t R, hipStr
     else
         hipLaunchKernelGGL((lyr_scatter0_kernel<DM, false>), grid, dim3(SC_NT), 0, st, a, D0);
 }
+// factored path: dm in {8, ..., 512} (fact_mode); false: no instantiation for dm
+static bool launch_scatter0_dm(int dm, const LyrArgs& a, const float* D0, int64_t R, hipStream_t st) {
+    switch (dm) {
+        case 8: launch_scatter0<8>(a, D0, R, st); return true;
+        case 16: launch_scatter0<16>(a, D0, R, st); return true;
+        case 32: launch_scatter0<32>(a, D0, R, st); return true;
+        case 64: launch_scatter0<64>(a, D0, R, st); return true;
+        case 128: launch_scatter0<128>(a, D0, R, st); return true;
+        case 256: launch_scatter0<256>(a, D0, R, st); return true;
+        case 512: launch_scatter0<512>(a, D0, R, st); return true;
+        default: return false;
+    }
+}
 
 // User side of the factored layer 0 after the step chain (UORD): D_0 rows already
 // sit in user order (position p of the rank slice at D0u + p * DM), so a walker of
@@ -2024,6 +1494,18 @@ static int launch_gemm_expand(const LyrArgs& a, float* Pj, hipStream_t st, const
     return hipGetLastError() == hipSuccess ? NCF_OK : NCF_E_LAUNCH;
 }
 
+// Launch kern<first, LD> (a per-layer kernel template) on lyr_run's stream with LD from
+// its `drop` and `vec`: dropout steps take ScalarDrop whatever factor_num is.
+#define NCF_LAUNCH_LD3(kern, FIRST, grid, ...)                                                              \
+    if (drop) hipLaunchKernelGGL((kern<FIRST, Ld::ScalarDrop>), grid, dim3(GNT), 0, st, __VA_ARGS__);       \
+    else if (vec) hipLaunchKernelGGL((kern<FIRST, Ld::Vec4>), grid, dim3(GNT), 0, st, __VA_ARGS__);         \
+    else hipLaunchKernelGGL((kern<FIRST, Ld::Scalar>), grid, dim3(GNT), 0, st, __VA_ARGS__)
+#define NCF_LAUNCH_LD(kern, first, grid, ...)                      \
+    do {                                                           \
+        if (first) { NCF_LAUNCH_LD3(kern, true, grid, __VA_ARGS__); } \
+        else { NCF_LAUNCH_LD3(kern, false, grid, __VA_ARGS__); }   \
+    } while (0)
+
 int lyr_run(const LyrArgs& a0, float* ws, int64_t R, bool train, hipStream_t st) {
     LyrArgs a = a0;
     const ncf_layout& lay = a.lay;
@@ -2112,17 +1594,8 @@ int lyr_run(const LyrArgs& a0, float* ws, int64_t R, bool train, hipStream_t st)
                 int64_t g0 = (R * (DM / 4) + GNT - 1) / GNT;
                 if (g0 > 8192) g0 = 8192;
                 hipLaunchKernelGGL(lyr_fwd0_fact_kernel, dim3((unsigned)g0), dim3(GNT), 0, st, a, Pj, H[1], R);
-            } else if (k == 0)
-                {
-                if (drop) hipLaunchKernelGGL((lyr_fwd_kernel<true, true, false>), grid, dim3(GNT), 0, st, a, k, nullptr, H[1], R);
-                else if (vec) hipLaunchKernelGGL((lyr_fwd_kernel<true, false, true>), grid, dim3(GNT), 0, st, a, k, nullptr, H[1], R);
-                else hipLaunchKernelGGL((lyr_fwd_kernel<true, false, false>), grid, dim3(GNT), 0, st, a, k, nullptr, H[1], R);
-            }
-            else
-                {
-                if (drop) hipLaunchKernelGGL((lyr_fwd_kernel<false, true, false>), grid, dim3(GNT), 0, st, a, k, H[k], H[k + 1], R);
-                else if (vec) hipLaunchKernelGGL((lyr_fwd_kernel<false, false, true>), grid, dim3(GNT), 0, st, a, k, H[k], H[k + 1], R);
-                else hipLaunchKernelGGL((lyr_fwd_kernel<false, false, false>), grid, dim3(GNT), 0, st, a, k, H[k], H[k + 1], R);
+            } else {
+                NCF_LAUNCH_LD(lyr_fwd_kernel, k == 0, grid, a, k, k == 0 ? nullptr : H[k], H[k + 1], R);
             }
         }
     }
@@ -2173,16 +1646,7 @@ int lyr_run(const LyrArgs& a0, float* ws, int64_t R, bool train, hipStream_t st)
         // with the user order the chain did the item runs and db_0 and left D_0 in user
         // order (the walk blocks of the launch above read it sequentially); without,
         // the full scatter
-#define NCF_L0(DD)                           \
-    case DD:                                 \
-        if (!a.uorder || wide)               \
-            launch_scatter0<DD>(a, cb.D[0], R, st);  \
-        break;
-        switch (DM) {
-            NCF_L0(8) NCF_L0(16) NCF_L0(32) NCF_L0(64) NCF_L0(128) NCF_L0(256) NCF_L0(512)
-            default: return NCF_E_UNSUPPORTED;
-        }
-#undef NCF_L0
+        if ((!a.uorder || wide) && !launch_scatter0_dm(DM, a, cb.D[0], R, st)) return NCF_E_UNSUPPORTED;
         if (DM > FACT_LDS_DM && launch_gemm_expand(a, Pj, st, w0img) != NCF_OK) return NCF_E_LAUNCH;
         return hipGetLastError() == hipSuccess ? NCF_OK : NCF_E_LAUNCH;
     }
@@ -2219,16 +1683,7 @@ int lyr_run(const LyrArgs& a0, float* ws, int64_t R, bool train, hipStream_t st)
     for (int k = L - 1; k >= 0; --k) {
         const int K = (2 * DM) >> k, J = K / 2;
         if (k == 0 && fact) {  // dY_0 into the table rows; dW0 / dUm / dIm by fact_expand_kernel
-            switch (DM) {  // factored path: dm in {8, ..., 512} (fact_mode)
-                case 8: launch_scatter0<8>(a, Dcur, R, st); break;
-                case 16: launch_scatter0<16>(a, Dcur, R, st); break;
-                case 32: launch_scatter0<32>(a, Dcur, R, st); break;
-                case 64: launch_scatter0<64>(a, Dcur, R, st); break;
-                case 128: launch_scatter0<128>(a, Dcur, R, st); break;
-                case 256: launch_scatter0<256>(a, Dcur, R, st); break;
-                case 512: launch_scatter0<512>(a, Dcur, R, st); break;
-                default: return NCF_E_UNSUPPORTED;
-            }
+            if (!launch_scatter0_dm(DM, a, Dcur, R, st)) return NCF_E_UNSUPPORTED;
             if (DM > FACT_LDS_DM && launch_gemm_expand(a, Pj, st) != NCF_OK) return NCF_E_LAUNCH;
             break;
         }
@@ -2242,31 +1697,10 @@ int lyr_run(const LyrArgs& a0, float* ws, int64_t R, bool train, hipStream_t st)
         chunk = (chunk + GBK - 1) / GBK * GBK;
         splits = (R + chunk - 1) / chunk;
         const dim3 gw((unsigned)((J + GBM - 1) / GBM), (unsigned)((K + GBN - 1) / GBN), (unsigned)splits);
-        if (k == 0)
-            {
-                if (drop) hipLaunchKernelGGL((lyr_bwd_w_kernel<true, true, false>), gw, dim3(GNT), 0, st, a, k, Dcur, nullptr, R, chunk);
-                else if (vec) hipLaunchKernelGGL((lyr_bwd_w_kernel<true, false, true>), gw, dim3(GNT), 0, st, a, k, Dcur, nullptr, R, chunk);
-                else hipLaunchKernelGGL((lyr_bwd_w_kernel<true, false, false>), gw, dim3(GNT), 0, st, a, k, Dcur, nullptr, R, chunk);
-            }
-        else
-            {
-                if (drop) hipLaunchKernelGGL((lyr_bwd_w_kernel<false, true, false>), gw, dim3(GNT), 0, st, a, k, Dcur, H[k], R, chunk);
-                else if (vec) hipLaunchKernelGGL((lyr_bwd_w_kernel<false, false, true>), gw, dim3(GNT), 0, st, a, k, Dcur, H[k], R, chunk);
-                else hipLaunchKernelGGL((lyr_bwd_w_kernel<false, false, false>), gw, dim3(GNT), 0, st, a, k, Dcur, H[k], R, chunk);
-            }
+        NCF_LAUNCH_LD(lyr_bwd_w_kernel, k == 0, gw, a, k, Dcur, k == 0 ? nullptr : H[k], R, chunk);
         const dim3 gd(mt, (unsigned)((K + GBN - 1) / GBN));
-        if (k == 0) {
-            {
-                if (drop) hipLaunchKernelGGL((lyr_bwd_data_kernel<true, true, false>), gd, dim3(GNT), 0, st, a, k, Dcur, nullptr, nullptr, R);
-                else if (vec) hipLaunchKernelGGL((lyr_bwd_data_kernel<true, false, true>), gd, dim3(GNT), 0, st, a, k, Dcur, nullptr, nullptr, R);
-                else hipLaunchKernelGGL((lyr_bwd_data_kernel<true, false, false>), gd, dim3(GNT), 0, st, a, k, Dcur, nullptr, nullptr, R);
-            }
-        } else {
-            {
-                if (drop) hipLaunchKernelGGL((lyr_bwd_data_kernel<false, true, false>), gd, dim3(GNT), 0, st, a, k, Dcur, H[k], Dnext, R);
-                else if (vec) hipLaunchKernelGGL((lyr_bwd_data_kernel<false, false, true>), gd, dim3(GNT), 0, st, a, k, Dcur, H[k], Dnext, R);
-                else hipLaunchKernelGGL((lyr_bwd_data_kernel<false, false, false>), gd, dim3(GNT), 0, st, a, k, Dcur, H[k], Dnext, R);
-            }
+        NCF_LAUNCH_LD(lyr_bwd_data_kernel, k == 0, gd, a, k, Dcur, k == 0 ? nullptr : H[k], k == 0 ? nullptr : Dnext, R);
+        if (k > 0) {
             float* tmp = Dcur;
             Dcur = Dnext;
             Dnext = tmp;
@@ -2274,5 +1708,7 @@ int lyr_run(const LyrArgs& a0, float* ws, int64_t R, bool train, hipStream_t st)
     }
     return hipGetLastError() == hipSuccess ? NCF_OK : NCF_E_LAUNCH;
 }
+#undef NCF_LAUNCH_LD
+#undef NCF_LAUNCH_LD3
 
 }  // namespace ncf

@@ -24,7 +24,8 @@ extern "C" {
 /* 21: pairwise (BPR) training: NCF_DZ_BPR of ncf_train_step, ncf_build_pair_stream.
  * Added within 21 (purely additive, the version is unchanged; probe with dlsym):
  * ncf_neighbors_workspace_bytes, ncf_neighbors; ncf_fold_opt, ncf_fold_in_workspace_bytes,
- * ncf_fold_in, ncf_debug_set_fold_path.
+ * ncf_fold_in, ncf_debug_set_fold_path; ncf_select_negatives_workspace_bytes,
+ * ncf_select_negatives, ncf_debug_set_select_path.
  * 20: full-catalogue top-K inference: ncf_recommend_workspace_bytes, ncf_recommend,
  * ncf_debug_set_recommend_path.
  * 19: NCF_LAYOUT_FACT_IN_ADAM (0x20) removed -- measured slower than the two launches it
@@ -772,6 +773,48 @@ int ncf_fold_in(const ncf_layout *lay, const float *params,
  * through the generic path whatever the shape; 0 restores the choice from the layout.
  * NCF_E_ARG otherwise. */
 int ncf_debug_set_fold_path(int path);
+
+/*
+ * Dynamic negative sampling for the pairwise mode (NCF_DZ_BPR): per positive, the hardest
+ * of its m sampled candidates under the current parameters.  Added within ABI 21
+ * (NCF_ABI_VERSION is unchanged: the addition is purely additive); probe with dlsym before
+ * calling into a library that may predate it.  The reference has nothing of the kind.
+ *
+ * For group p < n (user users[p], candidates cand[p * m .. p * m + m), the neg layout of
+ * ncf_build_rows / ncf_build_pair_stream): j* = argmax_j logit(users[p], cand[p * m + j]),
+ * the logit being NCF.forward in eval mode (models.py:97-118; dropout is never applied),
+ * equal scores resolving to the lowest j; neg_out[p] = cand[p * m + j*], slot_out[p] = j*
+ * and score_out[p] = that logit (either may be NULL).  Duplicate ids inside a group are
+ * legal.  The caller range-checks the ids, as for ncf_forward.  Group p's result depends on
+ * that group alone: not on n, on the group's position or on the other groups.  Nothing is
+ * written past entry n - 1; nothing is allocated or synchronised (the call can be captured).
+ * 1 <= m <= 64, else NCF_E_ARG; n == 0 returns NCF_OK; a null required pointer or a workspace
+ * below ncf_select_negatives_workspace_bytes (-1 from that: bad argument) gives NCF_E_ARG.
+ *
+ * Two paths, chosen as ncf_recommend chooses (every shape ncf_supported accepts):
+ *   NCF_PATH_FUSED shapes with dm <= 64: ncf_recommend's prologue (Pi over the catalogue;
+ *     Pu and Ag over the n rows' users, or over the user table when n >= user_num) and one
+ *     kernel that scores 16 pairs per MFMA tile -- the arithmetic sequence of ncf_recommend,
+ *     so a pair's score has the bits ncf_recommend gives it -- and reduces each group across
+ *     lanes; one store per group and output.  Workspace: (item_num + R) * max(16, dm) +
+ *     R * max(16, f) floats, R = min(n, user_num), each array rounded up to 256 bytes.
+ *   other shapes: in chunks of whole groups of at most 131,072 pairs, the packed rows are
+ *     written, ncf_forward scores them and a select kernel applies the same rule.
+ *     Workspace: 12 bytes per pair of one chunk plus ncf_forward_workspace_bytes of it.
+ */
+int64_t ncf_select_negatives_workspace_bytes(const ncf_layout *lay, int64_t n, int m);
+int ncf_select_negatives(const ncf_layout *lay, const float *params,
+                         const int32_t *users /* [n] */,
+                         const int32_t *cand /* [n * m], group p = cand[p*m .. p*m+m) */,
+                         int64_t n, int m,
+                         int32_t *neg_out /* [n] chosen item id */,
+                         int32_t *slot_out /* [n] chosen j, or NULL */,
+                         float *score_out /* [n] its logit, or NULL */,
+                         void *workspace, int64_t workspace_bytes, void *stream);
+/* Tests only: NCF_PATH_LAYERED sends later ncf_select_negatives calls (and their workspace
+ * sizes) through the materialised path whatever the shape; 0 restores the choice from the
+ * layout.  NCF_E_ARG otherwise. */
+int ncf_debug_set_select_path(int path);
 
 /* Diagnostics only: ablation switches for the next ncf_train_step launches
  * (1 = skip embedding scatter-add, 2 = skip weight-gradient MFMAs).  Results are

@@ -31,7 +31,6 @@
 
 namespace ncf {
 
-constexpr int64_t RC_MAT_PAIRS = 1 << 17;  // materialised path: (user, item) pairs per chunk
 constexpr int RC_LDS_LIMIT = 160 * 1024;
 
 static int g_rc_path = 0;  // ncf_debug_set_recommend_path

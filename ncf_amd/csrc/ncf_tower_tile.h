@@ -15,6 +15,8 @@
 namespace ncf {
 
 constexpr int RC_CH = 64;  // items per LDS chunk of ncf_recommend (one seen-mask bit per lane)
+// materialised paths (ncf_recommend, ncf_select_negatives): (user, item) pairs per chunk
+constexpr int64_t RC_MAT_PAIRS = 1 << 17;
 
 __host__ __device__ constexpr int rc_max(int a, int b) { return a > b ? a : b; }
 

@@ -203,6 +203,43 @@ class NCF(nn.Module):
             out_s[b:b + c, :m] = torch.where(keep, val[:, :m], torch.full_like(val[:, :m], float("-inf")))
         return out_i, out_s
 
+    # ---------------------------------------------------------- hardest negatives
+    def hardest_negatives(self, users, candidates):
+        """Dynamic negative sampling: for every row, the candidate the model currently
+        scores highest.  ``users`` [n], ``candidates`` [n, m] (1 <= m <= 64; duplicate ids
+        inside a row are fine) -> ``ops.HardNegatives(items int64 [n], slots int64 [n],
+        scores float32 [n])`` on the model's device: the chosen item, its column in the
+        row and its score.  Scores are ``forward(u, i)`` in eval mode (dropout never
+        applies, whatever ``self.training``); equal scores resolve to the lowest column.
+        A row's result depends on that row alone.  IndexError for an id outside the
+        tables, ValueError for a bad m or shape.
+
+        On a HIP device this is ``ncf_select_negatives`` (the fused score-and-select
+        kernel); a CPU model runs the same contract with stock torch ops."""
+        from . import ops
+        if self.embed_user_GMF.weight.is_cuda:
+            r = ops.select_negatives(self, users, candidates)
+            return ops.HardNegatives(r.items.to(torch.int64), r.slots.to(torch.int64), r.scores)
+        return self._hardest_cpu(users, candidates)
+
+    @torch.no_grad()
+    def _hardest_cpu(self, users, candidates):
+        from . import ops
+        u = torch.as_tensor(users).to(torch.int64)
+        c = torch.as_tensor(candidates).to(torch.int64)
+        n, m = ops.check_candidate_shape(u, c)
+        if n and (int(u.min()) < 0 or int(u.max()) >= self.user_num):
+            raise IndexError("index out of range in self (user id)")
+        if n and (int(c.min()) < 0 or int(c.max()) >= self.item_num):
+            raise IndexError("index out of range in self (item id)")
+        if n == 0:
+            return ops.HardNegatives(c.new_zeros(0), c.new_zeros(0), torch.zeros(0))
+        s = self._logits_eval(u.repeat_interleave(m), c.reshape(-1)).view(n, m)
+        best = s.max(dim=1, keepdim=True).values
+        slots = (s == best).to(torch.int64).argmax(dim=1)  # the first column holding the maximum
+        rows = torch.arange(n)
+        return ops.HardNegatives(c[rows, slots], slots, s[rows, slots])
+
     # ---------------------------------------------------------------- neighbours
     def similar_items(self, items, k=10, space=None, metric="cosine", exclude_self=True):
         """The k items whose learned embedding is most similar to each queried item's:

@@ -641,6 +641,83 @@ def neighbors(model, side, queries, k, space=None, metric="cosine", exclude_self
 
 
 # ---------------------------------------------------------------------------
+# dynamic negative sampling: the hardest of m candidates per positive (ncf_select_negatives;
+# added within ABI 21)
+MAX_CANDIDATES = 64  # ncf_select_negatives' limit on m
+
+
+class HardNegatives(collections.namedtuple("HardNegatives", "items slots scores")):
+    """Result of NCF.hardest_negatives: per group the chosen item id, its slot j in the
+    group and its logit."""
+    __slots__ = ()
+
+
+def check_candidates(m):
+    if isinstance(m, bool) or int(m) != m or not 1 <= int(m) <= MAX_CANDIDATES:
+        raise ValueError(f"candidates per positive must be an integer in [1, {MAX_CANDIDATES}], got {m!r}")
+    return int(m)
+
+
+@contextlib.contextmanager
+def _select_materialised():
+    """Tests: ncf_select_negatives through its materialised path whatever the shape."""
+    L.check(L.hip().ncf_debug_set_select_path(L.PATH_LAYERED), "ncf_debug_set_select_path")
+    try:
+        yield
+    finally:
+        L.hip().ncf_debug_set_select_path(0)
+
+
+def select_negatives_workspace(lay, n, m, owner, dev):
+    need = int(L.hip().ncf_select_negatives_workspace_bytes(L.ctypes.byref(lay), int(n), int(m)))
+    if need < 0:
+        raise ValueError("ncf_select_negatives_workspace_bytes failed")
+    return _ws(owner, "_ncf_sel_ws", need, dev)
+
+
+def select_negatives_into(flat, lay, users_i32, cand_i32, m, neg_out, slot_out, score_out, ws):
+    """One ncf_select_negatives call on the current stream into preallocated tensors
+    (capturable: nothing is allocated or synchronised).  users_i32 [n], cand_i32 [n * m]
+    (group p = cand[p * m .. p * m + m)); slot_out / score_out may be None."""
+    L.check(L.hip().ncf_select_negatives(L.ctypes.byref(lay), flat.data_ptr(), users_i32.data_ptr(),
+                                         cand_i32.data_ptr(), users_i32.numel(), int(m), neg_out.data_ptr(),
+                                         L.ptr(slot_out), L.ptr(score_out),
+                                         None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
+                                         L.stream_ptr(flat.device)), "ncf_select_negatives")
+
+
+def check_candidate_shape(users, candidates):
+    """(n, m) of users [n] and candidates [n, m]; ValueError for any other shape or a bad m."""
+    if candidates.dim() != 2 or users.dim() != 1 or candidates.shape[0] != users.shape[0]:
+        raise ValueError("hardest negatives: users [n] and candidates [n, m]")
+    return int(users.shape[0]), check_candidates(int(candidates.shape[1]))
+
+
+def select_negatives(model, users, candidates):
+    """HardNegatives (items int32 [n], slots int32 [n], scores float32 [n]) of a HIP-resident
+    model: per row the candidate with the highest eval-mode logit, equal scores to the
+    lowest slot."""
+    flat, lay = ensure_flat(model)
+    dev = flat.device
+    u = _as_i32(users, dev)
+    c = _as_i32(candidates, dev)
+    n, m = check_candidate_shape(u, c)
+    items = torch.empty(n, dtype=torch.int32, device=dev)
+    slots = torch.empty(n, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return HardNegatives(items, slots, scores)
+    lo_hi = torch.stack([u.min(), u.max(), c.min(), c.max()]).tolist()
+    if lo_hi[0] < 0 or lo_hi[1] >= model.user_num:
+        raise IndexError("index out of range in self (user id)")
+    if lo_hi[2] < 0 or lo_hi[3] >= model.item_num:
+        raise IndexError("index out of range in self (item id)")
+    ws = select_negatives_workspace(lay, n, m, model, dev)
+    select_negatives_into(flat, lay, u, c.view(-1), m, items, slots, scores, ws)
+    return HardNegatives(items, slots, scores)
+
+
+# ---------------------------------------------------------------------------
 # fold-in: vectors for unseen users from their interaction lists (ncf_fold_in; added within ABI 21)
 class FoldExamples(collections.namedtuple("FoldExamples", "ptr items labels")):
     """Examples of Q folded users: ptr int64 [Q + 1], items int32 [E], labels float32 [E]

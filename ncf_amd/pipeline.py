@@ -26,7 +26,10 @@ epoch e's steps, into the other of two output buffers (the step graphs are
 captured once per buffer), so the epoch boundary is one stream wait.
 EpochPipeline(pairwise=True) builds the pair stream of the BPR mode instead: the same
 sampler call and torch draws, ncf_randperm over the P * num_ng (user, item+, item-)
-triples and ncf_build_pair_stream (two rows per triple, no grouping).
+triples and ncf_build_pair_stream (two rows per triple, no grouping).  With select= (dynamic
+negative sampling) the epoch is P triples: the permutation over P is built ahead, the choice
+of each positive's negative among its num_ng candidates and the pair stream are made at
+the epoch boundary on the training stream, at the parameters of that moment.
 When epoch e+1 starts, the real draws are made and compared with what was used;
 a mismatch (someone else consumed either generator in between) discards the
 prefetch, and the epoch is built synchronously.
@@ -116,7 +119,7 @@ class EpochPipeline:
     depth + 1 sets of buffers, one being trained from."""
 
     def __init__(self, dataset, device, batch_size, item_num, user_num=None, prefetch=True, depth=None,
-                 canonical=None, pairwise=False):
+                 canonical=None, pairwise=False, select=None):
         """canonical: rows of one item inside a batch in (user, label) order
         (ncf_prepare_epoch2 NCF_PREP_CANONICAL) -- every rank of a data-parallel group
         then builds the identical stream; None: on when torch.distributed runs more
@@ -125,7 +128,20 @@ class EpochPipeline:
         sampler call and the DataLoader's same two torch draws, then a
         DataLoader(shuffle=True) order over the S = P * num_ng (user, item+, item-)
         triples: ncf_randperm over S and ncf_build_pair_stream into the slot's 2 S-row
-        output.  No item grouping; batch_size is unused."""
+        output.  No item grouping; batch_size is unused.
+        select (pairwise only): dynamic negative sampling.  The epoch is then P triples, one
+        per positive: the host staging is the same (one sampler call with num_ng candidates
+        per positive, the same two torch draws), the permutation is ncf_randperm over P
+        (P - 1 words), built ahead on the side stream into a per-slot buffer, and inside
+        next_epoch(), on the caller's stream, ``chosen = select(pos_users, candidates)``
+        (int32 device tensors [P] and [P, num_ng] -> int32 [P], e.g. a closure over
+        ops.select_negatives_into at the parameters of that moment) picks each positive's
+        negative and ncf_build_pair_stream writes the 2 P-row stream.  The selection is on
+        the training stream at the epoch boundary: it is not overlapped."""
+        self.pairwise = bool(pairwise)
+        self.select = select
+        if select is not None and not self.pairwise:
+            raise ValueError("select (dynamic negative sampling) needs pairwise=True")
         self.ds = dataset
         self.device = torch.device(device)
         self.batch_size = int(batch_size)
@@ -144,12 +160,11 @@ class EpochPipeline:
         self.pu = torch.as_tensor(pu, dtype=torch.int32).to(dev)
         self.pi = torch.as_tensor(pi, dtype=torch.int32).to(dev)
         self.S = self.P * self.ng
-        self.pairwise = bool(pairwise)
         if self.pairwise and self.ng == 0:
             raise ValueError("pairwise epochs need sampled negatives (num_ng > 0)")
         # n: entries the epoch's permutation orders (rows, or triples); n_out: rows of the stream
-        self.n = self.S if self.pairwise else self.P + self.S
-        self.n_out = 2 * self.S if self.pairwise else self.n
+        self.n = (self.P if select is not None else self.S) if self.pairwise else self.P + self.S
+        self.n_out = 2 * self.n if self.pairwise else self.n
         if depth is None:
             depth = int(os.environ.get("NCF_PIPE_DEPTH", "2"))
         self.depth = max(1, int(depth)) if prefetch else 0
@@ -157,7 +172,11 @@ class EpochPipeline:
         K = self.depth + 1
         # shared by the builds (issued in epoch order on one stream)
         self.rows = None if self.pairwise else torch.empty(self.n, dtype=torch.int64, device=dev)
-        self.perm = torch.empty(self.n, dtype=torch.int64, device=dev)
+        self.perm = torch.empty(self.n, dtype=torch.int64, device=dev) if select is None else None
+        # select: the pair stream is built later, on the caller's stream, so a prefetched
+        # build must not overwrite the permutation of an epoch not yet consumed
+        self._perm_slot = ([torch.empty(self.n, dtype=torch.int64, device=dev) for _ in range(K)]
+                           if select is not None else None)
         self.fy_ws = torch.empty(int(L.hip().ncf_randperm_workspace(self.n)), dtype=torch.uint8, device=dev)
         self.prep = ops.EpochPrep(dev, canonical=canonical)
         # per slot
@@ -177,7 +196,8 @@ class EpochPipeline:
         self._wordgen = WordsGen()
         self.events = None  # (start, rows+perm built, grouped) of the last epoch
         # on_built(rows_out, stream): called after each epoch's build, on the build's
-        # stream (the worker thread for a prefetched epoch), e.g. TrainEngine.owner_prebuild
+        # stream (the worker thread for a prefetched epoch; with select, next_epoch()'s caller and
+        # stream, where the pair stream is written), e.g. TrainEngine.owner_prebuild
         self.on_built = None
 
     # ---------------------------------------------------------------- host part
@@ -240,10 +260,14 @@ class EpochPipeline:
             L.check(lib.ncf_build_rows(self.pu.data_ptr(), self.pi.data_ptr(), self.P,
                                        self._neg_dev[slot].data_ptr() if self.S else None, self.ng,
                                        self.rows.data_ptr(), st), "ncf_build_rows")
-        L.check(lib.ncf_randperm(self._words_dev[slot].data_ptr(), self.n, self.perm.data_ptr(),
+        perm = self.perm if self.select is None else self._perm_slot[slot]
+        L.check(lib.ncf_randperm(self._words_dev[slot].data_ptr(), self.n, perm.data_ptr(),
                                  self.fy_ws.data_ptr(), self.fy_ws.numel(), st), "ncf_randperm")
         staged.built = torch.cuda.Event(enable_timing=True)
         staged.built.record(stream)
+        if self.select is not None:  # the pair stream waits for the selection: _select_build
+            staged.ready = staged.built
+            return
         if self.pairwise:  # the triples in permutation order, two rows each (no grouping)
             L.check(lib.ncf_build_pair_stream(self.pu.data_ptr(), self.pi.data_ptr(), self.P,
                                               self._neg_dev[slot].data_ptr(), self.ng, self.perm.data_ptr(),
@@ -257,6 +281,23 @@ class EpochPipeline:
         if hook is not None:  # per-stream work of the consumer, on the same stream (e.g. owner lists)
             with torch.cuda.stream(stream):
                 hook(self._out[slot], stream)
+
+    def _select_build(self, slot, cur):
+        """Dynamic negative sampling, on the caller's stream `cur` (after the staged uploads
+        and the slot's permutation): the hardest candidate per positive at the current
+        parameters, then the P triples in permutation order into the slot's output."""
+        with torch.cuda.stream(cur):
+            chosen = self.select(self.pu, self._neg_dev[slot][: self.S].view(self.P, self.ng))
+        if (not isinstance(chosen, torch.Tensor) or chosen.dtype != torch.int32 or chosen.numel() != self.P
+                or not chosen.is_contiguous() or chosen.device != self.pu.device):
+            raise ValueError("select must return a contiguous int32 device tensor with one item per positive")
+        L.check(L.hip().ncf_build_pair_stream(self.pu.data_ptr(), self.pi.data_ptr(), self.P, chosen.data_ptr(), 1,
+                                              self._perm_slot[slot].data_ptr(), self._out[slot].data_ptr(),
+                                              cur.cuda_stream), "ncf_build_pair_stream")
+        hook = self.on_built
+        if hook is not None:
+            with torch.cuda.stream(cur):
+                hook(self._out[slot], cur)
 
     def _launch(self, seed, prev, key=None, pos=None):
         """Stage the epoch after `prev` (or from (key, pos)) on a worker thread."""
@@ -351,6 +392,8 @@ class EpochPipeline:
         # randint draws leave the cached Gaussian of the legacy state alone
         np.random.set_state(("MT19937", staged.end_key, staged.end_pos, gauss[0], gauss[1]))
         cur.wait_event(staged.ready)
+        if self.select is not None:
+            self._select_build(staged.slot, cur)
         # everything that read the previous epoch's slot (its steps; a build on this
         # stream) is enqueued before this point
         if self._cur_slot is not None:

@@ -33,29 +33,49 @@ from .engine import TrainEngine
 from .metrics import evaluate_rows_device
 
 
-def bpr_host_epoch(ds):
+def bpr_host_epoch(ds, select=None):
     """One pairwise (BPR) epoch built on the host (the NCF_HOST_EPOCH=1 path of
     Trainer(loss="bpr")): the reference's ng_sample() (NumPy global stream), the
     DataLoader(shuffle=True) protocol's two torch draws and a randperm over the
     S = P * num_ng triples (data.epoch_permutation), packed by ops.bpr_stream_host.
-    Returns the 2 S packed rows (int64 numpy)."""
+    Returns the 2 S packed rows (int64 numpy).
+    select (dynamic negative sampling): ``chosen = select(pos_users [P], candidates
+    [P, num_ng])`` (int32 arrays in, one item id per positive out) picks each positive's
+    negative; the randperm is then over the P triples and the result has 2 P rows."""
     ds.ng_sample()
     _, items, _ = ds.arrays()
     P, ng = len(ds._ps_u), int(ds.num_ng)
-    perm = epoch_permutation(P * ng).numpy()
-    return ops.bpr_stream_host(ds._ps_u, ds._ps_i, items[P:], ng, perm)
+    if select is None:
+        perm = epoch_permutation(P * ng).numpy()
+        return ops.bpr_stream_host(ds._ps_u, ds._ps_i, items[P:], ng, perm)
+    perm = epoch_permutation(P).numpy()
+    chosen = np.asarray(select(ds._ps_u, np.ascontiguousarray(items[P:], dtype=np.int32).reshape(P, ng)))
+    if chosen.shape != (P,):
+        raise ValueError("select must return one item per positive")
+    return ops.bpr_stream_host(ds._ps_u, ds._ps_i, chosen, 1, perm)
 
 
 class Trainer:
     def __init__(self, model, train_dataset: NCFData, test_loader=None, *, batch_size=256, lr=1e-3,
                  optimizer="adam", top_k=10, device=None, world_size=1, rank=0, process_group=None,
-                 use_graph=True, save_path=None, verbose=True, test_batch=None, distill=None, loss="bce"):
+                 use_graph=True, save_path=None, verbose=True, test_batch=None, distill=None, loss="bce",
+                 negatives="uniform"):
         """distill: a distillation module (ncf_amd.distill) whose student is `model`:
         every step then trains the student on that module's loss (device plan).
         loss: "bce" (the reference loop) or "bpr" -- the pairwise ranking loss: an epoch
         is a DataLoader(shuffle=True) pass over the P * num_ng (user, item+, item-)
         triples of ng_sample(), batch_size counts triples (the engine gets
-        2 * batch_size rows per batch) and Loss= is the mean BPR loss per triple."""
+        2 * batch_size rows per batch) and Loss= is the mean BPR loss per triple.
+        negatives (loss "bpr" only): "uniform" trains on every sampled negative; "hard" is
+        dynamic negative sampling -- at each epoch's start the num_ng sampled candidates of
+        every positive are scored with the parameters of that moment (those an evaluate()
+        would see; ncf_select_negatives) and the epoch trains on the P triples (user,
+        item+, highest-scoring candidate).  The selection runs on the training stream at
+        the epoch boundary; it is not overlapped with the previous epoch."""
+        if negatives not in ("uniform", "hard"):
+            raise ValueError(f"negatives {negatives!r}: 'uniform' or 'hard'")
+        if negatives == "hard" and loss != "bpr":
+            raise ValueError("negatives 'hard' (dynamic negative sampling) needs loss 'bpr'")
         self.model = model
         self.ds = train_dataset
         self.test_loader = test_loader
@@ -73,7 +93,10 @@ class Trainer:
             raise ValueError(f"loss {loss!r}")
         if loss == "bpr" and int(train_dataset.num_ng) == 0:
             raise ValueError("loss 'bpr' needs sampled negatives (num_ng > 0)")
+        if negatives == "hard":
+            ops.check_candidates(int(train_dataset.num_ng))  # the candidates per positive: 1 .. 64
         self.loss = loss
+        self.negatives = negatives
         # rows per engine batch: a BPR batch of batch_size triples is 2 * batch_size rows
         self._batch_rows = 2 * self.batch_size if loss == "bpr" else self.batch_size
         plan = distill.device_plan() if distill is not None else None
@@ -88,6 +111,28 @@ class Trainer:
         self._pipe = None
 
     # ------------------------------------------------------------------ data
+    def _select_hard(self, users_i32, cand_i32):
+        """negatives="hard": the hardest candidate of every positive (int32 device tensors
+        [P] and [P, num_ng] -> int32 [P]) on the current stream, at the engine's parameters
+        brought up to date (flush) -- the ones an evaluate() at this moment would see."""
+        self.engine.flush()
+        lay = self.model._ncf_layout
+        n, m = cand_i32.shape
+        if getattr(self, "_hard_out", None) is None or self._hard_out.numel() != n:
+            self._hard_out = torch.empty(n, dtype=torch.int32, device=self.device)
+        ws = ops.select_negatives_workspace(lay, n, m, self, self.device)
+        ops.select_negatives_into(self.engine.flat, lay, users_i32, cand_i32.reshape(-1), m, self._hard_out, None,
+                                  None, ws)
+        return self._hard_out
+
+    def _select_hard_host(self, users, cand):
+        """_select_hard for the host-built epoch: NumPy int32 arrays in, the chosen ids out
+        (the ids are range-checked first: the kernel gathers with them)."""
+        ops.check_ids(users, cand, int(self.model.user_num), int(self.model.item_num))
+        u = torch.as_tensor(np.ascontiguousarray(users, dtype=np.int32)).to(self.device)
+        c = torch.as_tensor(np.ascontiguousarray(cand, dtype=np.int32)).to(self.device)
+        return self._select_hard(u, c).cpu().numpy()
+
     def _epoch_stream(self):
         """ng_sample + DataLoader order for one epoch -> device stream in batch order.
         Default: the epoch pipeline (ncf_amd.pipeline: the next epoch's negatives and
@@ -99,14 +144,15 @@ class Trainer:
                 from .pipeline import EpochPipeline
                 self._pipe = EpochPipeline(self.ds, self.device, self.batch_size, int(self.model.item_num),
                                            user_num=int(self.model.user_num), canonical=self.world_size > 1,
-                                           pairwise=self.loss == "bpr")
+                                           pairwise=self.loss == "bpr",
+                                           select=self._select_hard if self.negatives == "hard" else None)
                 self.engine.stream_buffers = self._pipe.buffers  # step graphs captured for both
                 self._pipe.on_built = self.engine.owner_prebuild  # dp_mode "owner": lists built with each epoch
             # fit() evaluates after every epoch (one torch draw): the next epoch's
             # sampler seed is peeked past it
             return self._pipe.next_epoch(peek_eval_draw=True)
         if self.loss == "bpr":
-            pairs = bpr_host_epoch(self.ds)
+            pairs = bpr_host_epoch(self.ds, select=self._select_hard_host if self.negatives == "hard" else None)
             u, i, _ = self.ds.arrays()
             ops.check_ids(u, i, int(self.model.user_num), int(self.model.item_num))
             if getattr(self, "_rows", None) is None or self._rows.numel() != pairs.size:

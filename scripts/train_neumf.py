@@ -64,11 +64,14 @@ def train_neumf(args, device):
     print(f"Model parameters: {param_count:,}")
     opt, lr = ("sgd", args.lr * 10) if args.pretraining else ("adam", args.lr)
     trainer = Trainer(model, train_dataset, test_loader, batch_size=args.batch_size, lr=lr, optimizer=opt,
-                      top_k=args.top_k, device=device, loss=args.loss)
+                      top_k=args.top_k, device=device, loss=args.loss, negatives=args.negatives)
     print(f"Training for {args.epochs} epochs...")
     suffix = "pre" if args.pretraining else "end"
-    # a pairwise (BPR) run never overwrites a BCE checkpoint: "_bpr" before "_best.pth"
+    # a pairwise (BPR) run never overwrites a BCE checkpoint: "_bpr" before "_best.pth";
+    # a run with dynamic negative sampling never overwrites a "_bpr" one: "_bpr_hard"
     tag = "_bpr" if args.loss == "bpr" else ""
+    if args.negatives == "hard":
+        tag += "_hard"
     fname = f"NeuMF_{suffix}_{args.num_layers}l_{args.factor_num}f{tag}_best.pth"
 
     def save(m):
@@ -108,8 +111,13 @@ def main():
     p.add_argument("--loss", type=str, default="bce", choices=["bce", "bpr"],
                    help="bce: the reference objective; bpr: pairwise ranking loss over (user, item+, item-) "
                         "triples (batch_size then counts triples)")
+    p.add_argument("--negatives", type=str, default="uniform", choices=["uniform", "hard"],
+                   help="with --loss bpr: uniform trains on every sampled negative; hard (dynamic negative "
+                        "sampling) on the highest-scoring of each positive's num_ng candidates, chosen per epoch")
     p.add_argument("--seed", type=int, default=None, help="seed numpy + torch (the reference never seeds)")
     args = p.parse_args()
+    if args.negatives == "hard" and args.loss != "bpr":
+        p.error("--negatives hard is only valid with --loss bpr")
     if args.seed is not None:
         np.random.seed(args.seed)
         torch.manual_seed(args.seed)

@@ -5,8 +5,8 @@
 //   loss_q = mean_e BCEWithLogits(logit(ug, um, items[e]), labels[e]),  e in [ptr[q], ptr[q+1]).
 // The whole optimisation of a user runs inside one launch: one workgroup per user.
 //
-// Prologue (both paths, one launch): Pi = Im W0[:, dm:]^T + b0 over the catalogue, the fmaf
-// chain of rc_proj_chain per element (the bits of ncf_recommend's Pi); the step scalars
+// Prologue (both paths, one launch): Pi = Im W0[:, dm:]^T + b0 over the catalogue, tile_pi
+// per element (ncf_tower_tile.h: the bits of ncf_recommend's Pi); the step scalars
 // (-lr / (1 - beta1^t), sqrt(1 - beta2^t)) of t = t0 + 1 .. t0 + steps, once, by
 // step_pair (ncf_adam.h): the two double pows are not evaluated inside the step loop; and,
 // for calls of at most FD_ORDER_MAX users, the users ordered longest list first (workgroup b
@@ -14,18 +14,20 @@
 // and start first -- 41.1 -> 27.0 ms at the benchmark shape then).  A user's
 // result does not depend on its position, so the order changes no bit.
 //
-// Fused path (the shapes of ncf_recommend's fused path, dm <= 64).  A workgroup of 4 waves
-// stages in LDS the tower weights W_1 .. W_{L-1} in the layout rc_layer reads, a
-// transposed image of each for the data-gradient pass, the biases, the predict weights and
-// W0[:, :dm] (row stride dm + 1).  Per step:
+// Fused path (NCF_FUSED_SHAPES, dm <= 64).  A workgroup of 4 waves stages in LDS the tower
+// weights W_1 .. W_{L-1} in the layout rc_layer reads and, in the same pass, a transposed
+// image of each for the data-gradient pass (its own loop, not tile_stage: fold_kernel is
+// compiled to a register budget and keeps the code it was tuned with), the biases, the
+// predict weights and W0[:, :dm] (row stride dm + 1).  Per step:
 //   1. Pu = W0u um (thread c: the fmaf chain over k), Ag = wp_g * ug.
 //   2. Wave w walks the 16-example tiles w, w + 4, ...: lane (g, it) gathers its columns of
 //      the Pi row and the embed_item_GMF row of example `it` by item id (L2-resident
-//      tables; streamed every step), h0 = relu(Pu + Pi), layers 1.. on
-//      v_mfma_f32_16x16x4_f32 (rc_layer), the logit, dz = (sigmoid(z) - y) / n (0 past the
-//      user's last example), back through the tower on the same MFMA with the transposed
-//      images and the ReLU masks of the activations still in registers, and per lane, in
-//      tile order, acc += dpre0 ([dm]) and acc += dz * ig ([f]).
+//      tables; streamed every step), h0 = relu(Pu + Pi) (tile_h0), layers 1.. on
+//      v_mfma_f32_16x16x4_f32 (rc_layer), the logit (tile_gmf_dot, tile_logit),
+//      dz = (sigmoid(z) - y) / n (0 past the user's last example), back through the tower
+//      on the same MFMA with the transposed images and the ReLU masks of the activations
+//      still in registers, and per lane, in tile order, acc += dpre0 ([dm]) and
+//      acc += dz * ig ([f]).
 //   3. Reduction in a fixed order: butterfly over the 16 item lanes (xor 1, 2, 4, 8), then
 //      waves 0, 1, 2, 3 summed left to right from LDS.
 //   4. dum = W0u^T S (thread k: the fmaf chain over c), dug = wp_g * Sg.
@@ -43,8 +45,7 @@
 // numbers -- not for speed.
 #include <string.h>
 
-#include "ncf_adam.h"
-#include "ncf_common.h"
+#include "ncf_host.h"
 #include "ncf_tower_tile.h"
 
 namespace ncf {
@@ -52,7 +53,6 @@ namespace ncf {
 static int g_fold_path = 0;  // ncf_debug_set_fold_path
 
 constexpr int FD_THREADS = RC_WAVES * 64;
-constexpr int FD_LDS_LIMIT = 160 * 1024;
 constexpr int FD_ORDER_MAX = 16384;  // users: the rank pass is quadratic; beyond, the tail is a small share
 
 struct FoldArgs {
@@ -105,15 +105,7 @@ __global__ __launch_bounds__(256) void fold_pro_kernel(ncf_layout lay, const flo
     int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx < n_pi) {
         const int64_t row = idx / kpi;
-        const int c = (int)(idx - row * kpi);
-        float acc = 0.f;
-        if (c < DM) {
-            const float* w = prm + lay.w[0] + (int64_t)c * 2 * DM + DM;
-            const float* x = prm + lay.im + row * DM;
-            acc = rc_proj_chain(x, w, DM);
-            acc += prm[lay.b[0] + c];
-        }
-        Pi[idx] = acc;
+        Pi[idx] = tile_pi(lay, prm, row, (int)(idx - row * kpi), DM);
         return;
     }
     idx -= n_pi;
@@ -308,13 +300,9 @@ __global__ __launch_bounds__(FD_THREADS, 2) void fold_kernel(FoldArgs a) {
             float part = 0.f;
             if constexpr (C::MLP) {
 #pragma unroll
-                for (int t = 0; t < T0; ++t) {
-                    const f4 pi = *reinterpret_cast<const f4*>(a.Pi + (int64_t)item * C::KP0 + 16 * t + 4 * g);
-                    h0[t].x = fmaxf(pu[t].x + pi.x, 0.f);
-                    h0[t].y = fmaxf(pu[t].y + pi.y, 0.f);
-                    h0[t].z = fmaxf(pu[t].z + pi.z, 0.f);
-                    h0[t].w = fmaxf(pu[t].w + pi.w, 0.f);
-                }
+                for (int t = 0; t < T0; ++t)
+                    h0[t] = tile_h0(pu[t],
+                                    *reinterpret_cast<const f4*>(a.Pi + (int64_t)item * C::KP0 + 16 * t + 4 * g));
                 if constexpr (C::NL >= 1) rc_layer(h0, h1, Wl + C::woff(1), Bl + C::boff(1), it, g);
                 if constexpr (C::NL >= 2) rc_layer(h1, h2, Wl + C::woff(2), Bl + C::boff(2), it, g);
                 if constexpr (C::NL >= 3) rc_layer(h2, h3, Wl + C::woff(3), Bl + C::boff(3), it, g);
@@ -323,23 +311,8 @@ __global__ __launch_bounds__(FD_THREADS, 2) void fold_kernel(FoldArgs a) {
                 if constexpr (C::NL == 2) part = rc_dot(h2, WPl, g);
                 if constexpr (C::NL == 3) part = rc_dot(h3, WPl, g);
             }
-            if constexpr (C::GMF) {
-                float sg = 0.f;
-#pragma unroll
-                for (int t = 0; t < TG; ++t) {
-                    ig[t] = f4{0.f, 0.f, 0.f, 0.f};
-                    if (16 * t + 4 * g < F)  // F % 8 == 0 on this path: whole float4s
-                        ig[t] = *reinterpret_cast<const f4*>(prm + a.lay.ig + (int64_t)item * F + 16 * t + 4 * g);
-                    sg = fmaf(ag[t].x, ig[t].x, sg);
-                    sg = fmaf(ag[t].y, ig[t].y, sg);
-                    sg = fmaf(ag[t].z, ig[t].z, sg);
-                    sg = fmaf(ag[t].w, ig[t].w, sg);
-                }
-                part += sg;
-            }
-            part += shfl_xor(part, 16);
-            part += shfl_xor(part, 32);
-            const float z = part + bp;  // the same bits in the four lanes of an example
+            if constexpr (C::GMF) part += tile_gmf_dot<C>(ag, ig, prm + a.lay.ig + (int64_t)item * F, g);
+            const float z = tile_logit(part, bp);  // the same bits in the four lanes of an example
             const float dz = valid ? (sigmoidf_(z) - y) / nf : 0.f;
             if (valid && g == 0) lacc += bce_loss(z, y);
 
@@ -663,55 +636,17 @@ __global__ __launch_bounds__(FD_THREADS) void fold_generic_kernel(FoldArgs a, Fg
     }
 }
 
-struct FoldEntry {
-    int mode, F, L;
-    const void* fn;
-    int kp0;
-};
-
 template <int F, int L, int MODE>
-static FoldEntry fold_make() {
-    return FoldEntry{MODE, F, L, reinterpret_cast<const void*>(&fold_kernel<F, L, MODE>), RcShape<F, L, MODE>::KP0};
-}
-
-// The shapes of ncf_recommend's fused path (rc_entry, ncf_recommend.hip).
-static const FoldEntry* fold_entry(const ncf_layout* lay) {
-    static const FoldEntry table[] = {
-        fold_make<8, 1, NCF_MODEL_GMF>(),  fold_make<16, 1, NCF_MODEL_GMF>(),
-        fold_make<32, 1, NCF_MODEL_GMF>(), fold_make<64, 1, NCF_MODEL_GMF>(),
-#define NCF_FD_TOWER(F, L) fold_make<F, L, NCF_MODEL_MLP>(), fold_make<F, L, NCF_MODEL_NEUMF>()
-        NCF_FD_TOWER(8, 1),  NCF_FD_TOWER(8, 2),  NCF_FD_TOWER(8, 3),  NCF_FD_TOWER(8, 4),  NCF_FD_TOWER(16, 1),
-        NCF_FD_TOWER(16, 2), NCF_FD_TOWER(16, 3), NCF_FD_TOWER(32, 1), NCF_FD_TOWER(32, 2), NCF_FD_TOWER(64, 1),
-#undef NCF_FD_TOWER
-    };
-    const int Lk = lay->model_type == NCF_MODEL_GMF ? 1 : lay->num_layers;
-    for (const FoldEntry& e : table)
-        if (e.mode == lay->model_type && e.F == lay->factor_num && e.L == Lk) return &e;
-    return nullptr;
-}
-
-static const FoldEntry* fold_fused(const ncf_layout* lay) {
-    if (g_fold_path == NCF_PATH_LAYERED) return nullptr;
-    if (ncf_supported(lay->model_type, lay->factor_num, lay->num_layers) != NCF_PATH_FUSED) return nullptr;
-    return fold_entry(lay);
-}
-
-static int64_t fold_al(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+struct FoldKernel {
+    static constexpr auto kernel = &fold_kernel<F, L, MODE>;
+};
+static const TileEntry* fold_fused(const ncf_layout* lay) { return tile_fused<FoldKernel>(lay, g_fold_path); }
 
 // Pi columns per item: the fused kernel's padded width, dm on the generic path, 0 for GMF.
 static int fold_kpi(const ncf_layout* lay) {
     if (lay->model_type == NCF_MODEL_GMF) return 0;
-    const FoldEntry* e = fold_fused(lay);
+    const TileEntry* e = fold_fused(lay);
     return e ? e->kp0 : lay->factor_num << (lay->num_layers - 1);
-}
-
-static int fold_ensure_lds(const void* fn, int64_t bytes) {
-    static int64_t have = 64 * 1024;
-    if (bytes <= have) return NCF_OK;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-        return NCF_E_LAUNCH;
-    have = bytes;
-    return NCF_OK;
 }
 
 }  // namespace ncf
@@ -730,8 +665,8 @@ int64_t ncf_fold_in_workspace_bytes(const ncf_layout* lay, int64_t n_users, int6
     if (!lay || n_users < 0 || n_examples < 0 || steps < 1 || lay->item_num <= 0) return -1;
     if (!ncf_supported(lay->model_type, lay->factor_num, lay->num_layers)) return -1;
     if (n_users == 0) return 0;
-    return fold_al((int64_t)lay->item_num * fold_kpi(lay) * 4) + fold_al((int64_t)steps * 8) +
-           (n_users <= FD_ORDER_MAX ? fold_al(n_users * 4) : 0);
+    return ws_align((int64_t)lay->item_num * fold_kpi(lay) * 4) + ws_align((int64_t)steps * 8) +
+           (n_users <= FD_ORDER_MAX ? ws_align(n_users * 4) : 0);
 }
 
 int ncf_fold_in(const ncf_layout* lay, const float* params, const int64_t* ex_ptr, const int32_t* ex_items,
@@ -768,9 +703,9 @@ int ncf_fold_in(const ncf_layout* lay, const float* params, const int64_t* ex_pt
     a.loss_out = loss_out;
     a.grad_out = grad_out;
     a.Pi = reinterpret_cast<const float*>(ws);
-    a.sc = reinterpret_cast<const float*>(ws + fold_al(n_pi * 4));
+    a.sc = reinterpret_cast<const float*>(ws + ws_align(n_pi * 4));
     const bool ordered = n_users <= FD_ORDER_MAX;
-    if (ordered) a.order = reinterpret_cast<const int32_t*>(ws + fold_al(n_pi * 4) + fold_al((int64_t)opt->steps * 8));
+    if (ordered) a.order = reinterpret_cast<const int32_t*>(ws + ws_align(n_pi * 4) + ws_align((int64_t)opt->steps * 8));
     a.kpi = kpi;
     a.steps = opt->steps;
     a.eps = opt->eps;
@@ -779,12 +714,13 @@ int ncf_fold_in(const ncf_layout* lay, const float* params, const int64_t* ex_pt
     a.b2 = (float)opt->beta2;
     a.omb2 = (float)(1.0 - opt->beta2);
 
-    const FoldEntry* e = fold_fused(lay);
+    const TileEntry* e = fold_fused(lay);
     const FgShape sh = fg_shape(lay->factor_num, lay->factor_num << (lay->num_layers - 1));
     const int64_t lds = ((int64_t)sh.total * 4 + 15) & ~(int64_t)15;
     if (!e) {
-        if (lds > FD_LDS_LIMIT) return NCF_E_UNSUPPORTED;
-        if (fold_ensure_lds(reinterpret_cast<const void*>(&fold_generic_kernel), lds) != NCF_OK) return NCF_E_LAUNCH;
+        if (lds > LDS_LIMIT_BYTES) return NCF_E_UNSUPPORTED;
+        if (lds > 64 * 1024 && ensure_lds(reinterpret_cast<const void*>(&fold_generic_kernel), lds) != NCF_OK)
+            return NCF_E_LAUNCH;
     }
     const int64_t npro = n_pi + opt->steps;
     const unsigned pro_blocks = (unsigned)((npro + 255) / 256);
@@ -799,7 +735,7 @@ int ncf_fold_in(const ncf_layout* lay, const float* params, const int64_t* ex_pt
     } else {
         hipLaunchKernelGGL(fold_generic_kernel, dim3((unsigned)n_users), dim3(FD_THREADS), (size_t)lds, st, a, sh);
     }
-    return hipGetLastError() == hipSuccess ? NCF_OK : NCF_E_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -17,6 +17,38 @@ int ensure_lds(const void* fn, int64_t bytes);  // hipFuncSetAttribute once per 
 Ranges make_ranges(const int64_t* ranges, int nranges, int* err);
 int diag_flags();  // ncf_debug_set_diag's value
 
+// Workspace layouts: every piece starts on a 256-byte boundary
+inline int64_t ws_align(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+
+// Materialised paths (ncf_recommend, ncf_select_negatives): packed rows, their logits and
+// ncf_forward's own workspace for chunks of at most `pairs` (user, item) pairs.
+struct MatWs {
+    int64_t rows, logits, fwd, fwd_bytes, total;
+};
+inline MatWs mat_ws(const ncf_layout* lay, int64_t pairs) {
+    MatWs w;
+    w.rows = 0;
+    w.logits = ws_align(pairs * 8);
+    w.fwd = w.logits + ws_align(pairs * 4);
+    w.fwd_bytes = ncf_forward_workspace_bytes(lay, pairs);
+    w.total = w.fwd + ws_align(w.fwd_bytes);
+    return w;
+}
+
+// Fused paths: the layer-0 projections Pi [item_num][kp0], Pu [user_rows][kp0] and
+// Ag [user_rows][fp] (rc_proj_kernel, ncf_tower_tile.h); total = the first byte after them.
+struct ProjWs {
+    int64_t pi, pu, ag, total;
+};
+inline ProjWs proj_ws(const ncf_layout* lay, int64_t user_rows, int kp0, int fp) {
+    ProjWs w;
+    w.pi = 0;
+    w.pu = ws_align((int64_t)lay->item_num * kp0 * 4);
+    w.ag = w.pu + ws_align(user_rows * kp0 * 4);
+    w.total = w.ag + ws_align(user_rows * fp * 4);
+    return w;
+}
+
 // ncf_step.hip: layout geometry
 const KernelEntry* train_fused(const ncf_layout* lay);  // fused kernel of a training step, or null (layered)
 int fact_dm(const ncf_layout* lay);

@@ -26,13 +26,12 @@
 // partial lists.
 #include <string.h>
 
-#include "ncf_common.h"
+#include "ncf_host.h"
 
 namespace ncf {
 
 constexpr int NB_QT = 16;  // queries per workgroup (the M of one MFMA tile)
 constexpr int NB_CH = 64;  // catalogue rows per chunk: 16 per wave
-constexpr int NB_LDS_LIMIT = 160 * 1024;
 
 struct NbSeg {
     int64_t off;  // first float of the table in params
@@ -213,8 +212,6 @@ __global__ __launch_bounds__(RC_WAVES * 64) void nb_kernel(NbArgs a) {
     }
 }
 
-static int64_t nb_al(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
-
 // Launch shape from the query count and the table: 16-query tiles, and as many chunk
 // splits as bring the grid to about four workgroups per compute unit.
 struct NbGeo {
@@ -239,9 +236,9 @@ struct NbWs {
 static NbWs nb_ws(int N, int64_t nq, int K, const NbGeo& G) {
     NbWs w;
     int64_t o = 0;
-    w.inv = o; o += nb_al((int64_t)N * 4);
-    w.ps = o; o += nb_al(nq * G.nsplit * K * 4);
-    w.pid = o; o += nb_al(nq * G.nsplit * K * 4);
+    w.inv = o; o += ws_align((int64_t)N * 4);
+    w.ps = o; o += ws_align(nq * G.nsplit * K * 4);
+    w.pid = o; o += ws_align(nq * G.nsplit * K * 4);
     w.total = o;
     return w;
 }
@@ -298,14 +295,8 @@ int ncf_neighbors(const ncf_layout* lay, const float* params, int side, int spac
     if (space != NCF_SPACE_MLP) add(item ? lay->ig : lay->ug, lay->factor_num);
     if (space != NCF_SPACE_GMF) add(item ? lay->im : lay->um, lay->factor_num << (lay->num_layers - 1));
     const int64_t lds = nb_lds_bytes(a.DP, K);
-    if (lds > NB_LDS_LIMIT) return NCF_E_UNSUPPORTED;
-    static int64_t lds_granted = 64 * 1024;
-    if (lds > lds_granted) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&nb_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return NCF_E_LAUNCH;
-        lds_granted = lds;
-    }
+    if (lds > LDS_LIMIT_BYTES) return NCF_E_UNSUPPORTED;
+    if (lds > 64 * 1024 && ensure_lds(reinterpret_cast<const void*>(&nb_kernel), lds) != NCF_OK) return NCF_E_LAUNCH;
     char* ws = static_cast<char*>(workspace);
     a.params = params;
     a.queries = queries;
@@ -326,7 +317,7 @@ int ncf_neighbors(const ncf_layout* lay, const float* params, int side, int spac
     hipLaunchKernelGGL(rc_merge_kernel<>, dim3((unsigned)((n_queries + RC_WAVES - 1) / RC_WAVES)), dim3(RC_WAVES * 64),
                        (size_t)RC_WAVES * 2 * K * 4, st, a.part_s, a.part_i, n_queries, G.nsplit, K, ids_out,
                        scores_out);
-    return hipGetLastError() == hipSuccess ? NCF_OK : NCF_E_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

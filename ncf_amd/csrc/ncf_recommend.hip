@@ -8,8 +8,9 @@
 // the predict dot and the GMF dot (user side pre-scaled by the predict weights).  No
 // per-pair gathers and no U x I array.
 //
-// The register layout of a 16-item tile, the layer step and the predict dot are in
-// ncf_tower_tile.h (shared with ncf_fold.hip).
+// The register layout of a 16-item tile, the projection prologue (rc_proj_kernel), the
+// staging of the tower and the pair score are in ncf_tower_tile.h, shared with
+// ncf_select.hip and ncf_fold.hip.
 //
 // A workgroup (4 waves) owns a tile of 4 or 16 queried users and a range of 64-item
 // chunks; each chunk (Pi rows, Ig rows) is staged once in LDS and shared by the tile's
@@ -26,12 +27,10 @@
 // mask, order and list.
 #include <string.h>
 
-#include "ncf_common.h"
+#include "ncf_host.h"
 #include "ncf_tower_tile.h"
 
 namespace ncf {
-
-constexpr int RC_LDS_LIMIT = 160 * 1024;
 
 static int g_rc_path = 0;  // ncf_debug_set_recommend_path
 
@@ -78,38 +77,6 @@ __device__ __forceinline__ unsigned long long rc_seen_mask(const int32_t* __rest
     return mask;
 }
 
-// Prologue: Pi (b0 folded in), Pu and Ag = wp[:F] * Ug[u], zero padded to KP0 / FP columns.
-__global__ __launch_bounds__(256) void rc_proj_kernel(ncf_layout lay, const float* __restrict__ prm,
-                                                      const int32_t* __restrict__ users, int64_t nq, int KP0, int FP,
-                                                      float* __restrict__ Pi, float* __restrict__ Pu,
-                                                      float* __restrict__ Ag) {
-    const int DM = lay.factor_num << (lay.num_layers - 1);
-    const int F = lay.factor_num;
-    const int64_t n_pi = (int64_t)lay.item_num * KP0, n_pu = nq * KP0, n_ag = nq * FP;
-    int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx < n_pi + n_pu) {
-        const bool item = idx < n_pi;
-        if (!item) idx -= n_pi;
-        const int64_t row = idx / KP0;
-        const int c = (int)(idx - row * KP0);
-        float acc = 0.f;
-        if (c < DM) {
-            const float* w = prm + lay.w[0] + (int64_t)c * 2 * DM + (item ? DM : 0);
-            const float* x = item ? prm + lay.im + row * DM : prm + lay.um + (int64_t)users[row] * DM;
-            acc = rc_proj_chain(x, w, DM);
-            if (item) acc += prm[lay.b[0] + c];
-        }
-        (item ? Pi : Pu)[idx] = acc;
-        return;
-    }
-    idx -= n_pi + n_pu;
-    if (idx < n_ag) {
-        const int64_t q = idx / FP;
-        const int f = (int)(idx - q * FP);
-        Ag[idx] = f < F ? prm[lay.wp + f] * prm[lay.ug + (int64_t)users[q] * F + f] : 0.f;
-    }
-}
-
 template <int F, int L, int MODE>
 __global__ __launch_bounds__(RC_WAVES * 64) void rc_kernel(RcArgs a) {
     using C = RcShape<F, L, MODE>;
@@ -134,23 +101,7 @@ __global__ __launch_bounds__(RC_WAVES * 64) void rc_kernel(RcArgs a) {
     const int cb = split * a.cps, ce = min(cb + a.cps, nchunks);
     const int64_t q0 = (int64_t)blockIdx.x * UT;
 
-    // tower weights (zero padded), biases, predict weights
-    if constexpr (C::MLP) {
-#pragma unroll
-        for (int k = 1; k <= C::NL; ++k) {
-            const int rows = C::KP(k), cols = C::KP(k - 1), sw = C::SW(k);
-            const int out = C::DM >> k, in = C::DM >> (k - 1);
-            const float* w = prm + a.lay.w[k];
-            for (int idx = tid; idx < rows * cols; idx += RC_WAVES * 64) {
-                const int r = idx / cols, c = idx - r * cols;
-                Wl[C::woff(k) + r * sw + c] = (r < out && c < in) ? w[r * in + c] : 0.f;
-            }
-            for (int idx = tid; idx < rows; idx += RC_WAVES * 64)
-                Bl[C::boff(k) + idx] = idx < out ? prm[a.lay.b[k] + idx] : 0.f;
-        }
-        for (int idx = tid; idx < C::WP; idx += RC_WAVES * 64)
-            WPl[idx] = idx < F ? prm[a.lay.wp + C::POFF + idx] : 0.f;
-    }
+    tile_stage<C, RC_WAVES * 64>(a.lay, prm, Wl, Bl, WPl, tid);
     const float bp = prm[a.lay.bp];
 
     for (int uu = 0; uu < a.upw; ++uu) {
@@ -215,37 +166,12 @@ __global__ __launch_bounds__(RC_WAVES * 64) void rc_kernel(RcArgs a) {
                 if constexpr (C::MLP) {
                     f4 h0[C::T(0)];
 #pragma unroll
-                    for (int t = 0; t < C::T(0); ++t) {
-                        const f4 p = *reinterpret_cast<const f4*>(PiL + row * C::SP + 16 * t + 4 * g);
-                        h0[t].x = fmaxf(pu[t].x + p.x, 0.f);
-                        h0[t].y = fmaxf(pu[t].y + p.y, 0.f);
-                        h0[t].z = fmaxf(pu[t].z + p.z, 0.f);
-                        h0[t].w = fmaxf(pu[t].w + p.w, 0.f);
-                    }
-                    if constexpr (C::NL == 0) {
-                        part = rc_dot(h0, WPl, g);
-                    } else {
-                        f4 h1[C::T(1)];
-                        rc_layer(h0, h1, Wl + C::woff(1), Bl + C::boff(1), it, g);
-                        if constexpr (C::NL == 1) {
-                            part = rc_dot(h1, WPl, g);
-                        } else {
-                            f4 h2[C::T(2)];
-                            rc_layer(h1, h2, Wl + C::woff(2), Bl + C::boff(2), it, g);
-                            if constexpr (C::NL == 2) {
-                                part = rc_dot(h2, WPl, g);
-                            } else {
-                                f4 h3[C::T(3)];
-                                rc_layer(h2, h3, Wl + C::woff(3), Bl + C::boff(3), it, g);
-                                part = rc_dot(h3, WPl, g);
-                            }
-                        }
-                    }
+                    for (int t = 0; t < C::T(0); ++t)
+                        h0[t] = tile_h0(pu[t], *reinterpret_cast<const f4*>(PiL + row * C::SP + 16 * t + 4 * g));
+                    part = tile_tower<C>(h0, Wl, Bl, WPl, it, g);
                 }
                 if constexpr (C::GMF) part += rc_dot(ag, IgL + row * C::SG, g);
-                part += shfl_xor(part, 16);
-                part += shfl_xor(part, 32);
-                const float z = part + bp;
+                const float z = tile_logit(part, bp);
                 const int item = c0 + row;
                 const bool valid = lane < 16 && item < I && !((seen >> row) & 1ull);
                 rc_feed(ls, li, K, z, item, valid, lane);
@@ -320,35 +246,11 @@ __global__ __launch_bounds__(RC_WAVES * 64) void rc_select_kernel(const float* _
     }
 }
 
-struct RcEntry {
-    int mode, F, L;
-    const void* fn;
-    int fixed, kp0, fp;  // LDS floats before the lists; padded Pi / Pu and Ag widths
-};
-
 template <int F, int L, int MODE>
-static RcEntry rc_make() {
-    using C = RcShape<F, L, MODE>;
-    return RcEntry{MODE, F, L, reinterpret_cast<const void*>(&rc_kernel<F, L, MODE>), C::FIXED, C::KP0, C::FP};
-}
-
-// The shapes of kernel_table (ncf_train.hip): every shape ncf_supported calls fused.
-static const RcEntry* rc_entry(const ncf_layout* lay) {
-    static const RcEntry table[] = {
-        rc_make<8, 1, NCF_MODEL_GMF>(),  rc_make<16, 1, NCF_MODEL_GMF>(),
-        rc_make<32, 1, NCF_MODEL_GMF>(), rc_make<64, 1, NCF_MODEL_GMF>(),
-#define NCF_RC_TOWER(F, L) rc_make<F, L, NCF_MODEL_MLP>(), rc_make<F, L, NCF_MODEL_NEUMF>()
-        NCF_RC_TOWER(8, 1),  NCF_RC_TOWER(8, 2),  NCF_RC_TOWER(8, 3),  NCF_RC_TOWER(8, 4),  NCF_RC_TOWER(16, 1),
-        NCF_RC_TOWER(16, 2), NCF_RC_TOWER(16, 3), NCF_RC_TOWER(32, 1), NCF_RC_TOWER(32, 2), NCF_RC_TOWER(64, 1),
-#undef NCF_RC_TOWER
-    };
-    const int Lk = lay->model_type == NCF_MODEL_GMF ? 1 : lay->num_layers;
-    for (const RcEntry& e : table)
-        if (e.mode == lay->model_type && e.F == lay->factor_num && e.L == Lk) return &e;
-    return nullptr;
-}
-
-static int64_t rc_al(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+struct RcKernel {
+    static constexpr auto kernel = &rc_kernel<F, L, MODE>;
+};
+static const TileEntry* rc_fused(const ncf_layout* lay) { return tile_fused<RcKernel>(lay, g_rc_path); }
 
 // Launch shape of the fused kernel from the query size and the catalogue: 16-user tiles
 // from 256 queried users up (4-user tiles below), and as many item splits as bring the
@@ -372,24 +274,23 @@ static RcGeo rc_geometry(int64_t nq, int I) {
     return G;
 }
 
-static int64_t rc_lds_bytes(const RcEntry* e, const RcGeo& G, int K) {
+static int64_t rc_lds_bytes(const TileEntry* e, const RcGeo& G, int K) {
     const int UT = RC_WAVES * G.upw;
     // fixed, 2 UT K and the 256 scratch ints are even counts of 4-byte words: cur is 8-byte aligned
     return ((int64_t)e->fixed + 2 * UT * K + RC_WAVES * 64) * 4 + (int64_t)UT * 8;
 }
 
+// Workspace of the fused path: the projections, then the partial lists [nq][nsplit][K]
 struct RcFusedWs {
-    int64_t pi, pu, ag, ps, pid, total;
+    ProjWs p;
+    int64_t ps, pid, total;
 };
-static RcFusedWs rc_fused_ws(const RcEntry* e, const ncf_layout* lay, int64_t nq, int K, const RcGeo& G) {
+static RcFusedWs rc_fused_ws(const TileEntry* e, const ncf_layout* lay, int64_t nq, int K, const RcGeo& G) {
     RcFusedWs w;
-    int64_t o = 0;
-    w.pi = o; o += rc_al((int64_t)lay->item_num * e->kp0 * 4);
-    w.pu = o; o += rc_al(nq * e->kp0 * 4);
-    w.ag = o; o += rc_al(nq * e->fp * 4);
-    w.ps = o; o += rc_al(nq * G.nsplit * K * 4);
-    w.pid = o; o += rc_al(nq * G.nsplit * K * 4);
-    w.total = o;
+    w.p = proj_ws(lay, nq, e->kp0, e->fp);
+    w.ps = w.p.total;
+    w.pid = w.ps + ws_align(nq * G.nsplit * K * 4);
+    w.total = w.pid + ws_align(nq * G.nsplit * K * 4);
     return w;
 }
 
@@ -398,43 +299,6 @@ static int64_t rc_mat_users(const ncf_layout* lay, int64_t nq) {
     if (uc < 1) uc = 1;
     return uc < nq ? uc : nq;
 }
-
-struct RcMatWs {
-    int64_t rows, logits, fwd, fwd_bytes, total;
-};
-static RcMatWs rc_mat_ws(const ncf_layout* lay, int64_t nq) {
-    const int64_t pairs = rc_mat_users(lay, nq) * lay->item_num;
-    RcMatWs w;
-    int64_t o = 0;
-    w.rows = o; o += rc_al(pairs * 8);
-    w.logits = o; o += rc_al(pairs * 4);
-    w.fwd = o;
-    w.fwd_bytes = ncf_forward_workspace_bytes(lay, pairs);
-    o += rc_al(w.fwd_bytes);
-    w.total = o;
-    return w;
-}
-
-static bool rc_use_fused(const ncf_layout* lay) {
-    return g_rc_path != NCF_PATH_LAYERED &&
-           ncf_supported(lay->model_type, lay->factor_num, lay->num_layers) == NCF_PATH_FUSED && rc_entry(lay);
-}
-
-static int rc_ensure_lds(const void* fn, int64_t bytes) {
-    struct Slot { const void* fn; int64_t bytes; };
-    static Slot slots[64];
-    static int nslots = 0;
-    for (int i = 0; i < nslots; ++i)
-        if (slots[i].fn == fn && slots[i].bytes >= bytes) return NCF_OK;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-        return NCF_E_LAUNCH;
-    for (int i = 0; i < nslots; ++i)
-        if (slots[i].fn == fn) { slots[i].bytes = bytes; return NCF_OK; }
-    if (nslots < 64) slots[nslots++] = Slot{fn, bytes};
-    return NCF_OK;
-}
-
-static int rc_status() { return hipGetLastError() == hipSuccess ? NCF_OK : NCF_E_LAUNCH; }
 
 // ---------------------------------------------------------------------------
 // HR / NDCG per batch.  One wave per batch; the batch's logits staged in LDS.
@@ -494,9 +358,9 @@ int64_t ncf_recommend_workspace_bytes(const ncf_layout* lay, int64_t n_users, in
     if (!lay || n_users < 0 || top_k < 1 || top_k > RC_MAXK || lay->item_num <= 0) return -1;
     if (!ncf_supported(lay->model_type, lay->factor_num, lay->num_layers)) return -1;
     if (n_users == 0) return 0;
-    if (rc_use_fused(lay))
-        return rc_fused_ws(rc_entry(lay), lay, n_users, top_k, rc_geometry(n_users, lay->item_num)).total;
-    return rc_mat_ws(lay, n_users).total;
+    if (const TileEntry* e = rc_fused(lay))
+        return rc_fused_ws(e, lay, n_users, top_k, rc_geometry(n_users, lay->item_num)).total;
+    return mat_ws(lay, rc_mat_users(lay, n_users) * lay->item_num).total;
 }
 
 int ncf_recommend(const ncf_layout* lay, const float* params, const int32_t* users, int64_t n_users, int top_k,
@@ -512,13 +376,12 @@ int ncf_recommend(const ncf_layout* lay, const float* params, const int32_t* use
     char* ws = static_cast<char*>(workspace);
     const int I = lay->item_num, K = top_k;
 
-    if (rc_use_fused(lay)) {
-        const RcEntry* e = rc_entry(lay);
+    if (const TileEntry* e = rc_fused(lay)) {
         const RcGeo G = rc_geometry(n_users, I);
         const RcFusedWs W = rc_fused_ws(e, lay, n_users, K, G);
         const int64_t lds = rc_lds_bytes(e, G, K);
-        if (lds > RC_LDS_LIMIT) return NCF_E_UNSUPPORTED;
-        if (rc_ensure_lds(e->fn, lds) != NCF_OK) return NCF_E_LAUNCH;
+        if (lds > LDS_LIMIT_BYTES) return NCF_E_UNSUPPORTED;
+        if (ensure_lds(e->fn, lds) != NCF_OK) return NCF_E_LAUNCH;
         RcArgs a;
         memset(&a, 0, sizeof(a));
         a.lay = *lay;
@@ -528,16 +391,16 @@ int ncf_recommend(const ncf_layout* lay, const float* params, const int32_t* use
         a.K = K;
         a.seen_ptr = seen_ptr;
         a.seen_items = seen_items;
-        a.Pi = reinterpret_cast<float*>(ws + W.pi);
-        a.Pu = reinterpret_cast<float*>(ws + W.pu);
-        a.Ag = reinterpret_cast<float*>(ws + W.ag);
+        a.Pi = reinterpret_cast<float*>(ws + W.p.pi);
+        a.Pu = reinterpret_cast<float*>(ws + W.p.pu);
+        a.Ag = reinterpret_cast<float*>(ws + W.p.ag);
         a.part_s = reinterpret_cast<float*>(ws + W.ps);
         a.part_i = reinterpret_cast<int32_t*>(ws + W.pid);
         a.nsplit = G.nsplit;
         a.cps = G.cps;
         a.upw = G.upw;
         const int64_t nproj = ((int64_t)I + n_users) * e->kp0 + n_users * e->fp;
-        hipLaunchKernelGGL(rc_proj_kernel, dim3((unsigned)((nproj + 255) / 256)), dim3(256), 0, st, *lay, params,
+        hipLaunchKernelGGL(rc_proj_kernel<>, dim3((unsigned)((nproj + 255) / 256)), dim3(256), 0, st, *lay, params,
                            users, n_users, e->kp0, e->fp, const_cast<float*>(a.Pi), const_cast<float*>(a.Pu),
                            const_cast<float*>(a.Ag));
         void* args[] = {&a};
@@ -547,11 +410,11 @@ int ncf_recommend(const ncf_layout* lay, const float* params, const int32_t* use
         hipLaunchKernelGGL(rc_merge_kernel<>, dim3((unsigned)((n_users + RC_WAVES - 1) / RC_WAVES)), dim3(RC_WAVES * 64),
                            (size_t)RC_WAVES * 2 * K * 4, st, a.part_s, a.part_i, n_users, G.nsplit, K, items_out,
                            scores_out);
-        return rc_status();
+        return launch_status();
     }
 
-    const RcMatWs W = rc_mat_ws(lay, n_users);
     const int64_t ucmax = rc_mat_users(lay, n_users);
+    const MatWs W = mat_ws(lay, ucmax * I);
     uint64_t* rows = reinterpret_cast<uint64_t*>(ws + W.rows);
     float* logits = reinterpret_cast<float*>(ws + W.logits);
     for (int64_t qb = 0; qb < n_users; qb += ucmax) {
@@ -566,7 +429,7 @@ int ncf_recommend(const ncf_layout* lay, const float* params, const int32_t* use
                            (size_t)RC_WAVES * (2 * K + 64) * 4, st, logits, users, qb, uc, I, K, seen_ptr, seen_items,
                            items_out, scores_out);
     }
-    return rc_status();
+    return launch_status();
 }
 
 int ncf_hr_ndcg(const float* logits, const int32_t* items, int64_t n, int batch, int top_k, int32_t* hr, float* ndcg,
@@ -578,7 +441,7 @@ int ncf_hr_ndcg(const float* logits, const int32_t* items, int64_t n, int batch,
     const int64_t grid = (nb + 3) / 4;
     hipLaunchKernelGGL(hr_ndcg_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, logits, items, n, batch,
                        top_k, nb, hr, ndcg);
-    return rc_status();
+    return launch_status();
 }
 
 }  // extern "C"

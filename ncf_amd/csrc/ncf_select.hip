@@ -4,17 +4,17 @@
 // the hardest one -- the argmax of the eval-mode logit, equal scores to the lowest slot --
 // without materialising rows or logits.
 //
-// Fused path (the shapes of ncf_recommend's fused path, dm <= 64).  The prologue is
-// ncf_recommend's (the same expressions, the same bits): Pi = Im W0[:, dm:]^T + b0 over the
-// catalogue, Pu = Um W0[:, :dm]^T and Ag = wp * Ug over the n rows' users, or over the
-// whole user table when n >= user_num (row q = user id q then).  The main kernel runs
+// Fused path (NCF_FUSED_SHAPES, dm <= 64).  The prologue is ncf_recommend's (rc_proj_kernel,
+// ncf_tower_tile.h): Pi = Im W0[:, dm:]^T + b0 over the catalogue, Pu = Um W0[:, :dm]^T
+// and Ag = wp * Ug over the n rows' users, or over the whole user table when
+// n >= user_num (row q = user id q then).  The main kernel runs
 // workgroups of RC_WAVES waves with the tower weights, biases and predict weights staged in
 // LDS in the layout rc_layer reads.  A 16-column tile (ncf_tower_tile.h) holds 16 pairs:
 // lane (g, it) gathers its columns of Pu[user of it's group], Pi[cand], Ag and the
 // embed_item_GMF row from global memory (L2-resident tables, as ncf_fold.hip gathers),
-// h0 = relu(Pu + Pi), layers 1.. through rc_layer, rc_dot, the GMF dot, the two
-// shfl_xor(16 / 32) sums and + bp: the arithmetic sequence of rc_kernel, so a pair's score
-// has the bits ncf_recommend gives it.
+// then tile_h0, tile_tower, tile_gmf_dot and tile_logit: the functions rc_kernel scores a
+// pair with (its GMF dot reads the row from LDS, the same chain), so a pair's score has the
+// bits ncf_recommend gives it.
 //
 // Lanes of a tile.  m <= 16: a tile holds G = floor(16 / m) whole groups, group gi in
 // lanes it = gi m .. gi m + m - 1 (slot j = it - gi m); the lanes from G m on idle.  A
@@ -35,7 +35,7 @@
 // thread per group).  A second implementation for coverage, not for speed.
 #include <string.h>
 
-#include "ncf_common.h"
+#include "ncf_host.h"
 #include "ncf_tower_tile.h"
 
 namespace ncf {
@@ -61,41 +61,6 @@ struct SelArgs {
     float* score_out;
 };
 
-// Prologue: rc_proj_kernel's Pi, Pu and Ag (ncf_recommend.hip) with the user rows either
-// users[0 .. nr) (users != NULL) or the whole table (row = user id).
-__global__ __launch_bounds__(256) void sel_proj_kernel(ncf_layout lay, const float* __restrict__ prm,
-                                                       const int32_t* __restrict__ users, int64_t nr, int KP0, int FP,
-                                                       float* __restrict__ Pi, float* __restrict__ Pu,
-                                                       float* __restrict__ Ag) {
-    const int DM = lay.factor_num << (lay.num_layers - 1);
-    const int F = lay.factor_num;
-    const int64_t n_pi = (int64_t)lay.item_num * KP0, n_pu = nr * KP0, n_ag = nr * FP;
-    int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx < n_pi + n_pu) {
-        const bool item = idx < n_pi;
-        if (!item) idx -= n_pi;
-        const int64_t row = idx / KP0;
-        const int c = (int)(idx - row * KP0);
-        float acc = 0.f;
-        if (c < DM) {
-            const float* w = prm + lay.w[0] + (int64_t)c * 2 * DM + (item ? DM : 0);
-            const int64_t u = item ? row : (users != nullptr ? (int64_t)users[row] : row);
-            const float* x = item ? prm + lay.im + row * DM : prm + lay.um + u * DM;
-            acc = rc_proj_chain(x, w, DM);
-            if (item) acc += prm[lay.b[0] + c];
-        }
-        (item ? Pi : Pu)[idx] = acc;
-        return;
-    }
-    idx -= n_pi + n_pu;
-    if (idx < n_ag) {
-        const int64_t q = idx / FP;
-        const int f = (int)(idx - q * FP);
-        const int64_t u = users != nullptr ? (int64_t)users[q] : q;
-        Ag[idx] = f < F ? prm[lay.wp + f] * prm[lay.ug + u * F + f] : 0.f;
-    }
-}
-
 template <int F, int L, int MODE>
 __global__ __launch_bounds__(RC_WAVES * 64) void sel_kernel(SelArgs a) {
     using C = RcShape<F, L, MODE>;
@@ -105,28 +70,11 @@ __global__ __launch_bounds__(RC_WAVES * 64) void sel_kernel(SelArgs a) {
     float* const Wl = reinterpret_cast<float*>(smem4);
     float* const Bl = Wl + C::W_TOTAL;
     float* const WPl = Bl + C::B_TOTAL;
-    constexpr int T0 = C::MLP ? C::T(0) : 1, TG = C::GMF ? C::TG : 1;
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, it = lane & 15;
     const float* __restrict__ prm = a.params;
 
-    // tower weights (zero padded), biases, predict weights: rc_kernel's staging
-    if constexpr (C::MLP) {
-#pragma unroll
-        for (int k = 1; k <= C::NL; ++k) {
-            const int rows = C::KP(k), cols = C::KP(k - 1), sw = C::SW(k);
-            const int out = C::DM >> k, in = C::DM >> (k - 1);
-            const float* w = prm + a.lay.w[k];
-            for (int idx = tid; idx < rows * cols; idx += RC_WAVES * 64) {
-                const int r = idx / cols, c = idx - r * cols;
-                Wl[C::woff(k) + r * sw + c] = (r < out && c < in) ? w[r * in + c] : 0.f;
-            }
-            for (int idx = tid; idx < rows; idx += RC_WAVES * 64)
-                Bl[C::boff(k) + idx] = idx < out ? prm[a.lay.b[k] + idx] : 0.f;
-        }
-        for (int idx = tid; idx < C::WP; idx += RC_WAVES * 64)
-            WPl[idx] = idx < F ? prm[a.lay.wp + C::POFF + idx] : 0.f;
-    }
+    tile_stage<C, RC_WAVES * 64>(a.lay, prm, Wl, Bl, WPl, tid);
     const float bp = prm[a.lay.bp];
     __syncthreads();  // the only workgroup barrier: the waves walk their units on their own
 
@@ -153,55 +101,22 @@ __global__ __launch_bounds__(RC_WAVES * 64) void sel_kernel(SelArgs a) {
             const int64_t urow = valid ? (a.by_row ? p : (int64_t)a.users[p]) : 0;
             float part = 0.f;
             if constexpr (C::MLP) {
-                f4 h0[T0];
+                f4 h0[C::T(0)];
 #pragma unroll
-                for (int t = 0; t < T0; ++t) {
-                    const f4 pu = *reinterpret_cast<const f4*>(a.Pu + urow * C::KP0 + 16 * t + 4 * g);
-                    const f4 pi = *reinterpret_cast<const f4*>(a.Pi + (int64_t)cid * C::KP0 + 16 * t + 4 * g);
-                    h0[t].x = fmaxf(pu.x + pi.x, 0.f);
-                    h0[t].y = fmaxf(pu.y + pi.y, 0.f);
-                    h0[t].z = fmaxf(pu.z + pi.z, 0.f);
-                    h0[t].w = fmaxf(pu.w + pi.w, 0.f);
-                }
-                if constexpr (C::NL == 0) {
-                    part = rc_dot(h0, WPl, g);
-                } else {
-                    f4 h1[C::T(1)];
-                    rc_layer(h0, h1, Wl + C::woff(1), Bl + C::boff(1), it, g);
-                    if constexpr (C::NL == 1) {
-                        part = rc_dot(h1, WPl, g);
-                    } else {
-                        f4 h2[C::T(2)];
-                        rc_layer(h1, h2, Wl + C::woff(2), Bl + C::boff(2), it, g);
-                        if constexpr (C::NL == 2) {
-                            part = rc_dot(h2, WPl, g);
-                        } else {
-                            f4 h3[C::T(3)];
-                            rc_layer(h2, h3, Wl + C::woff(3), Bl + C::boff(3), it, g);
-                            part = rc_dot(h3, WPl, g);
-                        }
-                    }
-                }
+                for (int t = 0; t < C::T(0); ++t)
+                    h0[t] = tile_h0(*reinterpret_cast<const f4*>(a.Pu + urow * C::KP0 + 16 * t + 4 * g),
+                                    *reinterpret_cast<const f4*>(a.Pi + (int64_t)cid * C::KP0 + 16 * t + 4 * g));
+                part = tile_tower<C>(h0, Wl, Bl, WPl, it, g);
             }
             if constexpr (C::GMF) {
-                float sg = 0.f;  // rc_dot(ag, item row): the same chain, the row read from global memory
+                f4 ag[C::TG], ig[C::TG];
 #pragma unroll
-                for (int t = 0; t < TG; ++t) {
-                    const f4 ag = *reinterpret_cast<const f4*>(a.Ag + urow * C::FP + 16 * t + 4 * g);
-                    f4 ig = {0.f, 0.f, 0.f, 0.f};
-                    if (16 * t + 4 * g < F)  // F % 8 == 0 on this path: whole float4s
-                        ig = *reinterpret_cast<const f4*>(prm + a.lay.ig + (int64_t)cid * F + 16 * t + 4 * g);
-                    sg = fmaf(ag.x, ig.x, sg);
-                    sg = fmaf(ag.y, ig.y, sg);
-                    sg = fmaf(ag.z, ig.z, sg);
-                    sg = fmaf(ag.w, ig.w, sg);
-                }
-                part += sg;
+                for (int t = 0; t < C::TG; ++t)
+                    ag[t] = *reinterpret_cast<const f4*>(a.Ag + urow * C::FP + 16 * t + 4 * g);
+                part += tile_gmf_dot<C>(ag, ig, prm + a.lay.ig + (int64_t)cid * F, g);
             }
-            part += shfl_xor(part, 16);
-            part += shfl_xor(part, 32);
             // the group's best of this tile, in its first lane: suffix maximum over the item lanes
-            float bz = part + bp;
+            float bz = tile_logit(part, bp);
             int bj = j, bid = cid;
 #pragma unroll
             for (int d = 1; d < 16; d <<= 1) {
@@ -260,78 +175,18 @@ __global__ __launch_bounds__(256) void sel_pick_kernel(const float* __restrict__
     if (score_out != nullptr) score_out[p] = bz;
 }
 
-struct SelEntry {
-    int mode, F, L;
-    const void* fn;
-    int kp0, fp;
-};
-
 template <int F, int L, int MODE>
-static SelEntry sel_make() {
-    using C = RcShape<F, L, MODE>;
-    return SelEntry{MODE, F, L, reinterpret_cast<const void*>(&sel_kernel<F, L, MODE>), C::KP0, C::FP};
-}
-
-// The shapes of ncf_recommend's fused path (rc_entry, ncf_recommend.hip).
-static const SelEntry* sel_entry(const ncf_layout* lay) {
-    static const SelEntry table[] = {
-        sel_make<8, 1, NCF_MODEL_GMF>(),  sel_make<16, 1, NCF_MODEL_GMF>(),
-        sel_make<32, 1, NCF_MODEL_GMF>(), sel_make<64, 1, NCF_MODEL_GMF>(),
-#define NCF_SEL_TOWER(F, L) sel_make<F, L, NCF_MODEL_MLP>(), sel_make<F, L, NCF_MODEL_NEUMF>()
-        NCF_SEL_TOWER(8, 1),  NCF_SEL_TOWER(8, 2),  NCF_SEL_TOWER(8, 3),  NCF_SEL_TOWER(8, 4),  NCF_SEL_TOWER(16, 1),
-        NCF_SEL_TOWER(16, 2), NCF_SEL_TOWER(16, 3), NCF_SEL_TOWER(32, 1), NCF_SEL_TOWER(32, 2), NCF_SEL_TOWER(64, 1),
-#undef NCF_SEL_TOWER
-    };
-    const int Lk = lay->model_type == NCF_MODEL_GMF ? 1 : lay->num_layers;
-    for (const SelEntry& e : table)
-        if (e.mode == lay->model_type && e.F == lay->factor_num && e.L == Lk) return &e;
-    return nullptr;
-}
-
-static const SelEntry* sel_fused(const ncf_layout* lay) {
-    if (g_sel_path == NCF_PATH_LAYERED) return nullptr;
-    if (ncf_supported(lay->model_type, lay->factor_num, lay->num_layers) != NCF_PATH_FUSED) return nullptr;
-    return sel_entry(lay);
-}
-
-static int64_t sel_al(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+struct SelKernel {
+    static constexpr auto kernel = &sel_kernel<F, L, MODE>;
+};
+static const TileEntry* sel_fused(const ncf_layout* lay) { return tile_fused<SelKernel>(lay, g_sel_path); }
 
 // Rows of Pu / Ag: the call's rows when they are fewer than the users, else the user table.
 static int64_t sel_user_rows(const ncf_layout* lay, int64_t n) { return n < lay->user_num ? n : lay->user_num; }
 
-struct SelFusedWs {
-    int64_t pi, pu, ag, total;
-};
-static SelFusedWs sel_fused_ws(const SelEntry* e, const ncf_layout* lay, int64_t n) {
-    const int64_t R = sel_user_rows(lay, n);
-    SelFusedWs w;
-    int64_t o = 0;
-    w.pi = o; o += sel_al((int64_t)lay->item_num * e->kp0 * 4);
-    w.pu = o; o += sel_al(R * e->kp0 * 4);
-    w.ag = o; o += sel_al(R * e->fp * 4);
-    w.total = o;
-    return w;
-}
-
 static int64_t sel_mat_groups(int64_t n, int m) {
     const int64_t gc = RC_MAT_PAIRS / m;  // m <= 64: at least 2,048 groups
     return gc < n ? gc : n;
-}
-
-struct SelMatWs {
-    int64_t rows, logits, fwd, fwd_bytes, total;
-};
-static SelMatWs sel_mat_ws(const ncf_layout* lay, int64_t n, int m) {
-    const int64_t pairs = sel_mat_groups(n, m) * m;
-    SelMatWs w;
-    int64_t o = 0;
-    w.rows = o; o += sel_al(pairs * 8);
-    w.logits = o; o += sel_al(pairs * 4);
-    w.fwd = o;
-    w.fwd_bytes = ncf_forward_workspace_bytes(lay, pairs);
-    o += sel_al(w.fwd_bytes);
-    w.total = o;
-    return w;
 }
 
 }  // namespace ncf
@@ -350,8 +205,8 @@ int64_t ncf_select_negatives_workspace_bytes(const ncf_layout* lay, int64_t n, i
     if (!lay || n < 0 || m < 1 || m > SEL_MAXM || lay->item_num <= 0 || lay->user_num <= 0) return -1;
     if (!ncf_supported(lay->model_type, lay->factor_num, lay->num_layers)) return -1;
     if (n == 0) return 0;
-    const SelEntry* e = sel_fused(lay);
-    return e ? sel_fused_ws(e, lay, n).total : sel_mat_ws(lay, n, m).total;
+    const TileEntry* e = sel_fused(lay);
+    return e ? proj_ws(lay, sel_user_rows(lay, n), e->kp0, e->fp).total : mat_ws(lay, sel_mat_groups(n, m) * m).total;
 }
 
 int ncf_select_negatives(const ncf_layout* lay, const float* params, const int32_t* users, const int32_t* cand,
@@ -366,9 +221,9 @@ int ncf_select_negatives(const ncf_layout* lay, const float* params, const int32
     hipStream_t st = (hipStream_t)stream;
     char* ws = static_cast<char*>(workspace);
 
-    if (const SelEntry* e = sel_fused(lay)) {
-        const SelFusedWs W = sel_fused_ws(e, lay, n);
+    if (const TileEntry* e = sel_fused(lay)) {
         const int64_t R = sel_user_rows(lay, n);
+        const ProjWs W = proj_ws(lay, R, e->kp0, e->fp);
         SelArgs a;
         memset(&a, 0, sizeof(a));
         a.lay = *lay;
@@ -385,7 +240,7 @@ int ncf_select_negatives(const ncf_layout* lay, const float* params, const int32
         a.slot_out = slot_out;
         a.score_out = score_out;
         const int64_t nproj = ((int64_t)lay->item_num + R) * e->kp0 + R * e->fp;
-        hipLaunchKernelGGL(sel_proj_kernel, dim3((unsigned)((nproj + 255) / 256)), dim3(256), 0, st, *lay, params,
+        hipLaunchKernelGGL(rc_proj_kernel<>, dim3((unsigned)((nproj + 255) / 256)), dim3(256), 0, st, *lay, params,
                            a.by_row ? users : nullptr, R, e->kp0, e->fp, const_cast<float*>(a.Pi),
                            const_cast<float*>(a.Pu), const_cast<float*>(a.Ag));
         const int64_t units = m <= 16 ? (n + 16 / m - 1) / (16 / m) : n;
@@ -394,11 +249,11 @@ int ncf_select_negatives(const ncf_layout* lay, const float* params, const int32
         void* args[] = {&a};
         if (hipLaunchKernel(e->fn, dim3((unsigned)wgs), dim3(RC_WAVES * 64), args, 0, st) != hipSuccess)
             return NCF_E_LAUNCH;
-        return hipGetLastError() == hipSuccess ? NCF_OK : NCF_E_LAUNCH;
+        return launch_status();
     }
 
-    const SelMatWs W = sel_mat_ws(lay, n, m);
     const int64_t gcmax = sel_mat_groups(n, m);
+    const MatWs W = mat_ws(lay, gcmax * m);
     uint64_t* rows = reinterpret_cast<uint64_t*>(ws + W.rows);
     float* logits = reinterpret_cast<float*>(ws + W.logits);
     for (int64_t pb = 0; pb < n; pb += gcmax) {
@@ -412,7 +267,7 @@ int ncf_select_negatives(const ncf_layout* lay, const float* params, const int32
         hipLaunchKernelGGL(sel_pick_kernel, dim3((unsigned)((gc + 255) / 256)), dim3(256), 0, st, logits, cand, pb, gc,
                            m, neg_out, slot_out, score_out);
     }
-    return hipGetLastError() == hipSuccess ? NCF_OK : NCF_E_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -5,6 +5,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <vector>
+
 #include "ncf_host.h"
 
 namespace ncf {
@@ -140,18 +142,20 @@ constexpr int64_t GEO_MIN_WGS = NCF_GEO_MIN_WGS;
 int launch_status() { return hipGetLastError() == hipSuccess ? NCF_OK : NCF_E_LAUNCH; }
 
 // hipFuncSetAttribute once per (kernel, size): nothing but launches happen on
-// the hot path, so a step can be captured into a hipGraph.
+// the hot path, so a step can be captured into a hipGraph.  Every kernel of the library
+// with dynamic LDS comes through here (training, preparation and serving), so the pool
+// grows: a kernel is never dropped, and it is appended on its first call only.
 int ensure_lds(const void* fn, int64_t bytes) {
     struct Slot { const void* fn; int64_t bytes; };
-    static Slot slots[128];
-    static int nslots = 0;
-    for (int i = 0; i < nslots; ++i)
-        if (slots[i].fn == fn && slots[i].bytes >= bytes) return NCF_OK;
+    static std::vector<Slot> slots;
+    if (slots.capacity() == 0) slots.reserve(256);
+    for (const Slot& s : slots)
+        if (s.fn == fn && s.bytes >= bytes) return NCF_OK;
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
         return NCF_E_LAUNCH;
-    for (int i = 0; i < nslots; ++i)
-        if (slots[i].fn == fn) { slots[i].bytes = bytes; return NCF_OK; }
-    if (nslots < 128) slots[nslots++] = Slot{fn, bytes};
+    for (Slot& s : slots)
+        if (s.fn == fn) { s.bytes = bytes; return NCF_OK; }
+    slots.push_back(Slot{fn, bytes});
     return NCF_OK;
 }
 

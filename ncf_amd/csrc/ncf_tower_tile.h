@@ -1,6 +1,9 @@
-// The in-register MFMA tower tile shared by ncf_recommend.hip (full-catalogue top-K) and
-// ncf_fold.hip (fold-in of unseen users): the padded shape constants, the layer step, the
-// predict dot and the layer-0 projection chain.
+// The in-register MFMA tower tile shared by the serving entry points -- ncf_recommend.hip
+// (full-catalogue top-K), ncf_select.hip (hardest negatives) and ncf_fold.hip (fold-in of
+// unseen users): the list of fused shapes and the table built from it, the padded shape
+// constants, the layer-0 projection prologue, the staging of the tower into LDS, and the
+// pair score (h0, the layer ladder, the predict and GMF dots, the logit).  ncf_train.hip
+// builds kernel_table from the same shape list.
 //
 // Register layout of a 16-item tile of one user (one wave): lane l = (g = l >> 4,
 // it = l & 15) holds, for item `it`, the activations of columns 16 t + 4 g + r
@@ -11,6 +14,16 @@
 // with no transposes.  Widths below 16 are zero padded (weights, biases, Pi, Pu).
 #pragma once
 #include "ncf_common.h"
+
+// Every shape with a fused kernel (ncf_supported == NCF_PATH_FUSED), as X(F, L, MODE): the
+// one list behind kernel_table / kernel_table_bpr (ncf_train.hip) and the three serving
+// tables (tile_fused below).
+#define NCF_FUSED_TOWER(X, F, L) X(F, L, NCF_MODEL_MLP) X(F, L, NCF_MODEL_NEUMF)
+#define NCF_FUSED_SHAPES(X)                                                                                       \
+    X(8, 1, NCF_MODEL_GMF) X(16, 1, NCF_MODEL_GMF) X(32, 1, NCF_MODEL_GMF) X(64, 1, NCF_MODEL_GMF)                \
+    NCF_FUSED_TOWER(X, 8, 1) NCF_FUSED_TOWER(X, 8, 2) NCF_FUSED_TOWER(X, 8, 3) NCF_FUSED_TOWER(X, 8, 4)           \
+    NCF_FUSED_TOWER(X, 16, 1) NCF_FUSED_TOWER(X, 16, 2) NCF_FUSED_TOWER(X, 16, 3) NCF_FUSED_TOWER(X, 32, 1)       \
+    NCF_FUSED_TOWER(X, 32, 2) NCF_FUSED_TOWER(X, 64, 1)
 
 namespace ncf {
 
@@ -89,6 +102,159 @@ __device__ __forceinline__ float rc_proj_chain(const float* __restrict__ x, cons
     float acc = 0.f;
     for (int k = 0; k < n; ++k) acc = fmaf(x[k], w[k], acc);
     return acc;
+}
+
+// ---------------------------------------------------------------------------
+// The layer-0 projection prologue: pre0(u, i) = Pu[u] + Pi[i].  One element each, the fmaf
+// chain of rc_proj_chain and, for Pi, b0 added after it; columns from DM on are zero padding.
+__device__ __forceinline__ float tile_pi(const ncf_layout& lay, const float* prm, int64_t item, int c, int DM) {
+    if (c >= DM) return 0.f;
+    float acc = rc_proj_chain(prm + lay.im + item * DM, prm + lay.w[0] + (int64_t)c * 2 * DM + DM, DM);
+    acc += prm[lay.b[0] + c];
+    return acc;
+}
+__device__ __forceinline__ float tile_pu(const ncf_layout& lay, const float* prm, int64_t user, int c, int DM) {
+    return c < DM ? rc_proj_chain(prm + lay.um + user * DM, prm + lay.w[0] + (int64_t)c * 2 * DM, DM) : 0.f;
+}
+// Ag = wp[:F] * Ug[u]: the GMF user side pre-scaled by the predict weights
+__device__ __forceinline__ float tile_ag(const ncf_layout& lay, const float* prm, int64_t user, int f) {
+    return f < lay.factor_num ? prm[lay.wp + f] * prm[lay.ug + user * lay.factor_num + f] : 0.f;
+}
+
+// Pi [item_num][KP0] over the catalogue, Pu [nr][KP0] and Ag [nr][FP] over the user rows:
+// users[0 .. nr), or the user table (row = user id) with users == NULL.  A template so that
+// the translation units that launch it share one definition.
+template <int NT = 256>
+__global__ __launch_bounds__(NT) void rc_proj_kernel(ncf_layout lay, const float* __restrict__ prm,
+                                                     const int32_t* __restrict__ users, int64_t nr, int KP0, int FP,
+                                                     float* __restrict__ Pi, float* __restrict__ Pu,
+                                                     float* __restrict__ Ag) {
+    const int DM = lay.factor_num << (lay.num_layers - 1);
+    const int64_t n_pi = (int64_t)lay.item_num * KP0, n_pu = nr * KP0, n_ag = nr * FP;
+    int64_t idx = (int64_t)blockIdx.x * NT + threadIdx.x;
+    if (idx < n_pi) {
+        const int64_t row = idx / KP0;
+        Pi[idx] = tile_pi(lay, prm, row, (int)(idx - row * KP0), DM);
+        return;
+    }
+    idx -= n_pi;
+    const bool mlp = idx < n_pu;
+    if (!mlp) idx -= n_pu;
+    if (!mlp && idx >= n_ag) return;
+    const int64_t row = idx / (mlp ? KP0 : FP);
+    const int c = (int)(idx - row * (mlp ? KP0 : FP));
+    const int64_t u = users != nullptr ? (int64_t)users[row] : row;
+    if (mlp) Pu[idx] = tile_pu(lay, prm, u, c, DM);
+    else Ag[idx] = tile_ag(lay, prm, u, c);
+}
+
+// ---------------------------------------------------------------------------
+// Tower weights W_1 .. W_NL zero padded in the layout rc_layer reads, the biases and the
+// predict weights of the tower output into LDS, by the NT threads of a workgroup.  No
+// barrier: the caller's first one covers it.
+template <class C, int NT>
+__device__ __forceinline__ void tile_stage(const ncf_layout& lay, const float* prm, float* Wl, float* Bl, float* WPl,
+                                           int tid) {
+    if constexpr (C::MLP) {
+#pragma unroll
+        for (int k = 1; k <= C::NL; ++k) {
+            const int rows = C::KP(k), cols = C::KP(k - 1), sw = C::SW(k);
+            const int out = C::DM >> k, in = C::DM >> (k - 1);
+            const float* w = prm + lay.w[k];
+            for (int idx = tid; idx < rows * cols; idx += NT) {
+                const int r = idx / cols, c = idx - r * cols;
+                Wl[C::woff(k) + r * sw + c] = (r < out && c < in) ? w[r * in + c] : 0.f;
+            }
+            for (int idx = tid; idx < rows; idx += NT) Bl[C::boff(k) + idx] = idx < out ? prm[lay.b[k] + idx] : 0.f;
+        }
+        for (int idx = tid; idx < C::WP; idx += NT) WPl[idx] = idx < C::F ? prm[lay.wp + C::POFF + idx] : 0.f;
+    }
+}
+
+// h0 = relu(Pu + Pi), four columns
+__device__ __forceinline__ f4 tile_h0(const f4 pu, const f4 pi) {
+    f4 h;
+    h.x = fmaxf(pu.x + pi.x, 0.f);
+    h.y = fmaxf(pu.y + pi.y, 0.f);
+    h.z = fmaxf(pu.z + pi.z, 0.f);
+    h.w = fmaxf(pu.w + pi.w, 0.f);
+    return h;
+}
+
+// Layers 1 .. NL on h0 and the predict dot of the tower output: this lane's partial of the logit.
+template <class C>
+__device__ __forceinline__ float tile_tower(const f4 (&h0)[C::T(0)], const float* Wl, const float* Bl,
+                                            const float* WPl, int it, int g) {
+    if constexpr (C::NL == 0) {
+        return rc_dot(h0, WPl, g);
+    } else {
+        f4 h1[C::T(1)];
+        rc_layer(h0, h1, Wl + C::woff(1), Bl + C::boff(1), it, g);
+        if constexpr (C::NL == 1) {
+            return rc_dot(h1, WPl, g);
+        } else {
+            f4 h2[C::T(2)];
+            rc_layer(h1, h2, Wl + C::woff(2), Bl + C::boff(2), it, g);
+            if constexpr (C::NL == 2) {
+                return rc_dot(h2, WPl, g);
+            } else {
+                f4 h3[C::T(3)];
+                rc_layer(h2, h3, Wl + C::woff(3), Bl + C::boff(3), it, g);
+                return rc_dot(h3, WPl, g);
+            }
+        }
+    }
+}
+
+// rc_dot(ag, item row) with the embed_item_GMF row read from global memory into ig (zero
+// from column F on; F % 8 == 0 on the fused path: whole float4s).
+template <class C>
+__device__ __forceinline__ float tile_gmf_dot(const f4 (&ag)[C::TG], f4 (&ig)[C::TG], const float* row, int g) {
+    float sg = 0.f;
+#pragma unroll
+    for (int t = 0; t < C::TG; ++t) {
+        ig[t] = f4{0.f, 0.f, 0.f, 0.f};
+        if (16 * t + 4 * g < C::F) ig[t] = *reinterpret_cast<const f4*>(row + 16 * t + 4 * g);
+        sg = fmaf(ag[t].x, ig[t].x, sg);
+        sg = fmaf(ag[t].y, ig[t].y, sg);
+        sg = fmaf(ag[t].z, ig[t].z, sg);
+        sg = fmaf(ag[t].w, ig[t].w, sg);
+    }
+    return sg;
+}
+
+// The four column groups' partials summed across the wave, + bp: the same bits in the four
+// lanes of an item.
+__device__ __forceinline__ float tile_logit(float part, float bp) {
+    part += shfl_xor(part, 16);
+    part += shfl_xor(part, 32);
+    return part + bp;
+}
+
+// ---------------------------------------------------------------------------
+// One table per serving kernel template, over NCF_FUSED_SHAPES.  K<F, L, MODE>::kernel is
+// the kernel's address (function templates cannot be template arguments themselves).
+struct TileEntry {
+    int mode, F, L;
+    const void* fn;
+    int fixed, kp0, fp;  // ncf_recommend's LDS floats before the lists; padded Pi / Pu and Ag widths
+};
+
+// The fused kernel of a serving entry point for this layout, or null: its debug switch
+// (ncf_debug_set_*_path), then ncf_supported, then the table.
+template <template <int, int, int> class K>
+const TileEntry* tile_fused(const ncf_layout* lay, int debug_path) {
+#define NCF_TILE_ENTRY(F, L, MODE)                                                                          \
+    TileEntry{MODE, F, L, reinterpret_cast<const void*>(K<F, L, MODE>::kernel), RcShape<F, L, MODE>::FIXED, \
+              RcShape<F, L, MODE>::KP0, RcShape<F, L, MODE>::FP},
+    static const TileEntry table[] = {NCF_FUSED_SHAPES(NCF_TILE_ENTRY)};
+#undef NCF_TILE_ENTRY
+    if (debug_path == NCF_PATH_LAYERED) return nullptr;
+    if (ncf_supported(lay->model_type, lay->factor_num, lay->num_layers) != NCF_PATH_FUSED) return nullptr;
+    const int Lk = lay->model_type == NCF_MODEL_GMF ? 1 : lay->num_layers;
+    for (const TileEntry& e : table)
+        if (e.mode == lay->model_type && e.F == lay->factor_num && e.L == Lk) return &e;
+    return nullptr;
 }
 
 }  // namespace ncf

@@ -25,6 +25,7 @@
 
 #include "ncf_common.h"
 #include "ncf_kernels.h"
+#include "ncf_tower_tile.h"  // NCF_FUSED_SHAPES
 
 namespace ncf {
 
@@ -1510,12 +1511,9 @@ const NCF_TABLE_ENTRY* NCF_TABLE_FN(int* n) {
 #ifdef NCF_DEV_ONE
         make_entry<16, 3, NCF_MODEL_NEUMF>(),
 #else
-        make_entry<8, 1, NCF_MODEL_GMF>(),   make_entry<16, 1, NCF_MODEL_GMF>(),
-        make_entry<32, 1, NCF_MODEL_GMF>(),  make_entry<64, 1, NCF_MODEL_GMF>(),
-#define NCF_TOWER(F, L) make_entry<F, L, NCF_MODEL_MLP>(), make_entry<F, L, NCF_MODEL_NEUMF>()
-        NCF_TOWER(8, 1),  NCF_TOWER(8, 2),  NCF_TOWER(8, 3),  NCF_TOWER(8, 4),  NCF_TOWER(16, 1),
-        NCF_TOWER(16, 2), NCF_TOWER(16, 3), NCF_TOWER(32, 1), NCF_TOWER(32, 2), NCF_TOWER(64, 1),
-#undef NCF_TOWER
+#define NCF_TRAIN_ENTRY(F, L, MODE) make_entry<F, L, MODE>(),
+        NCF_FUSED_SHAPES(NCF_TRAIN_ENTRY)
+#undef NCF_TRAIN_ENTRY
 #endif
     };
     *n = (int)(sizeof(table) / sizeof(table[0]));

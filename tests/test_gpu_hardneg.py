@@ -129,16 +129,27 @@ def test_materialised_forced_agrees_with_fused():
 
 
 # --------------------------------------------------------------------------- 3. exact, against ncf_recommend
-@pytest.mark.parametrize("mt,f,Lyr", FUSED_MODELS)
+def _fused_shapes():
+    """Every shape with a fused kernel, from ncf_supported (the serving tables and the training
+    table are built from one list; GMF has no tower, so one layer count stands for it)."""
+    import ncf_amd._lib as L
+    return [(mt, f, Lyr) for mt in ("GMF", "MLP", "NeuMF-end") for f in range(1, 65) for Lyr in (1, 2, 3, 4)
+            if (mt != "GMF" or Lyr == 1) and L.supported(mt, f, Lyr) == 1]
+
+
+@pytest.mark.parametrize("mt,f,Lyr", FUSED_MODELS + [s for s in _fused_shapes() if s not in FUSED_MODELS])
 def test_fused_scores_are_recommend_bits(mt, f, Lyr):
     """I = 80 <= 128: recommend(all users, k = 80) yields every pair's score bit for bit; the
-    slot must be the first argmax of those bits over the group and the score those bits."""
+    slot must be the first argmax of those bits over the group and the score those bits.
+    FUSED_MODELS take the whole n x m grid; the other fused shapes n = 17 with m = 5 (an idle
+    lane, a partial tile) and m = 40 (three tiles per group)."""
+    full = (mt, f, Lyr) in FUSED_MODELS
     _, model = _small(mt, f, Lyr)
     it, sc = model.recommend(torch.arange(U), k=I, exclude=None)
     R = np.empty((U, I), dtype=np.float32)
     R[np.arange(U)[:, None], it.cpu().numpy()] = sc.cpu().numpy()
-    for n in (17, 1000):
-        for m in MS:
+    for n in ((17, 1000) if full else (17,)):
+        for m in (MS if full else (5, 40)):
             users, cand = H.draw(n, m, U, I, seed=5)
             if m >= 4:  # group 0: its user's best item twice, as the two best candidates
                 cand[0, 1] = cand[0, 3] = int(np.argmax(R[users[0]]))

@@ -25,7 +25,8 @@ extern "C" {
  * Added within 21 (purely additive, the version is unchanged; probe with dlsym):
  * ncf_neighbors_workspace_bytes, ncf_neighbors; ncf_fold_opt, ncf_fold_in_workspace_bytes,
  * ncf_fold_in, ncf_debug_set_fold_path; ncf_select_negatives_workspace_bytes,
- * ncf_select_negatives, ncf_debug_set_select_path.
+ * ncf_select_negatives, ncf_debug_set_select_path; ncf_rank_candidates_workspace_bytes,
+ * ncf_rank_candidates, ncf_debug_set_rank_path.
  * 20: full-catalogue top-K inference: ncf_recommend_workspace_bytes, ncf_recommend,
  * ncf_debug_set_recommend_path.
  * 19: NCF_LAYOUT_FACT_IN_ADAM (0x20) removed -- measured slower than the two launches it
@@ -815,6 +816,64 @@ int ncf_select_negatives(const ncf_layout *lay, const float *params,
  * sizes) through the materialised path whatever the shape; 0 restores the choice from the
  * layout.  NCF_E_ARG otherwise. */
 int ncf_debug_set_select_path(int path);
+
+/*
+ * Candidate ranking: the top_k of a caller-supplied item list per queried user (the second
+ * stage of a recommender: re-rank a retriever's candidates, rank the items in stock).  Added
+ * within ABI 21 (NCF_ABI_VERSION is unchanged: the addition is purely additive); probe with
+ * dlsym before calling into a library that may predate it.  The reference has nothing of
+ * the kind.
+ *
+ * List q < n_lists belongs to user users[q] and holds the item ids
+ * cand[cand_ptr[q] .. cand_ptr[q + 1]): cand_ptr is a device array of n_lists + 1 ascending
+ * offsets with cand_ptr[0] = 0 and cand_ptr[n_lists] = n_cand; the host never reads it (the
+ * launch geometry and the workspace size are functions of lay, n_lists, n_cand and top_k).
+ * A candidate's slot is its position inside its own list.  Entry r of list q
+ * (items_out / slots_out / scores_out [q * top_k + r]) is the r-th best candidate of that
+ * list: its item id, its slot and its logit, NCF.forward(users[q], item) in eval mode
+ * (models.py:97-118; dropout is never applied).  Order: score descending, then slot
+ * ascending -- a total order, and every score is one fixed arithmetic sequence, so a list's
+ * result depends on that list alone: not on n_lists, on the list's position, on the other
+ * lists, on the tiling or on any split of the work.  Duplicate ids inside a list are legal:
+ * every occurrence is its own entry (equal scores, the lower slot first).  A list shorter
+ * than top_k gets item -1, slot -1 and score -inf in its trailing entries (an empty list
+ * only those).  slots_out may be NULL.  The caller range-checks the ids, as for ncf_forward.
+ * Nothing is written past entry n_lists * top_k - 1; nothing is allocated or synchronised
+ * (the call can be captured).  1 <= top_k <= 128, else NCF_E_ARG; n_lists == 0 returns
+ * NCF_OK with nothing launched; a null required pointer, a negative count or a workspace
+ * below ncf_rank_candidates_workspace_bytes (-1 from that: bad argument) gives NCF_E_ARG; a
+ * shape ncf_supported refuses gives NCF_E_UNSUPPORTED.
+ *
+ * Two paths, chosen as ncf_recommend chooses (every shape ncf_supported accepts):
+ *   NCF_PATH_FUSED shapes with dm <= 64: ncf_recommend's prologue (Pi over the catalogue;
+ *     Pu and Ag over the call's rows, or over the user table when n_lists >= user_num) and
+ *     one kernel: a workgroup of four waves per list, 16 candidates per MFMA tile -- the
+ *     arithmetic sequence of ncf_recommend and ncf_select_negatives, so a pair's score has
+ *     the bits they give it -- and a running top-K list per wave keyed by the slot, merged
+ *     inside the workgroup.  Below 1,024 lists every list's tiles are split over
+ *     ceil(1024 / n_lists) <= 64 workgroups and a merge pass orders the partial lists.
+ *     Workspace: (item_num + R) * max(16, dm) + R * max(16, f) floats, R = min(n_lists,
+ *     user_num), and below 1,024 lists n_lists * splits * top_k (score, slot) pairs plus
+ *     n_lists * top_k slots, each array rounded up to 256 bytes.
+ *   other shapes: the flat candidate array in chunks of at most 131,072 pairs -- the packed
+ *     rows are written (each pair's list found by a search in cand_ptr) and ncf_forward
+ *     scores them into an n_cand-float array -- then one wave per list applies the same
+ *     order and list.  Workspace: 12 bytes per pair of one chunk, ncf_forward_workspace_bytes
+ *     of it and 4 n_cand bytes.
+ */
+int64_t ncf_rank_candidates_workspace_bytes(const ncf_layout *lay, int64_t n_lists, int64_t n_cand, int top_k);
+int ncf_rank_candidates(const ncf_layout *lay, const float *params,
+                        const int32_t *users    /* [n_lists] */,
+                        const int64_t *cand_ptr /* [n_lists + 1], device, ascending, cand_ptr[0] = 0 */,
+                        const int32_t *cand     /* [n_cand] item ids, list q = cand[cand_ptr[q] .. cand_ptr[q+1]) */,
+                        int64_t n_lists, int64_t n_cand, int top_k,
+                        int32_t *items_out /* [n_lists][k] */, int32_t *slots_out /* [n_lists][k] or NULL */,
+                        float *scores_out /* [n_lists][k] */,
+                        void *workspace, int64_t workspace_bytes, void *stream);
+/* Tests only: NCF_PATH_LAYERED sends later ncf_rank_candidates calls (and their workspace
+ * sizes) through the materialised path whatever the shape; 0 restores the choice from the
+ * layout.  NCF_E_ARG otherwise. */
+int ncf_debug_set_rank_path(int path);
 
 /* Diagnostics only: ablation switches for the next ncf_train_step launches
  * (1 = skip embedding scatter-add, 2 = skip weight-gradient MFMAs).  Results are

@@ -154,6 +154,10 @@ _HIP_PROTOS = {
     "ncf_select_negatives": (ctypes.c_int, [ctypes.POINTER(NcfLayout), c_vp, c_vp, c_vp, c_i64, ctypes.c_int, c_vp,
                                             c_vp, c_vp, c_vp, c_i64, c_vp]),
     "ncf_debug_set_select_path": (ctypes.c_int, [ctypes.c_int]),
+    "ncf_rank_candidates_workspace_bytes": (c_i64, [ctypes.POINTER(NcfLayout), c_i64, c_i64, ctypes.c_int]),
+    "ncf_rank_candidates": (ctypes.c_int, [ctypes.POINTER(NcfLayout), c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                           ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "ncf_debug_set_rank_path": (ctypes.c_int, [ctypes.c_int]),
     "ncf_hr_ndcg": (ctypes.c_int, [c_vp, c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "ncf_fact_mode": (ctypes.c_int, [c_vp]),
     "ncf_reduce_rows": (ctypes.c_int, [c_vp]),

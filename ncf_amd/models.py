@@ -240,6 +240,69 @@ class NCF(nn.Module):
         rows = torch.arange(n)
         return ops.HardNegatives(c[rows, slots], slots, s[rows, slots])
 
+    # ------------------------------------------------------------------- ranking
+    def rank(self, users, candidates, k=10):
+        """The k best of a caller-supplied item list per queried user (the second stage of a
+        recommender: re-rank a retriever's candidates, rank the items in stock):
+        ``ops.Ranked(items int64 [n, k], slots int64 [n, k], scores float32 [n, k])`` on the
+        model's device.  ``users`` [n]; ``candidates`` is an ``ops.CandidateLists``
+        (``ops.candidate_lists`` builds one from ragged lists), a 2-D ``[n, m]`` array (one
+        fixed-length list per row) or a 1-D array (one shared list for every queried user).
+        Scores are ``forward(u, i)`` in eval mode (dropout never applies, whatever
+        ``self.training``); order: score descending, then slot -- the candidate's position
+        in its own list -- ascending.  Duplicate ids inside a list are fine: every
+        occurrence is its own entry.  A list shorter than k gets item -1, slot -1 and score
+        -inf in the trailing entries.  A list's result depends on that list alone.
+        1 <= k <= 128.  IndexError for an id outside the tables; ValueError for a bad k or
+        shape, a non-monotone ``ptr`` or a ``users`` / ``ptr`` length mismatch.
+
+        On a HIP device this is ``ncf_rank_candidates`` (the fused score-and-select
+        kernel); a CPU model runs the same contract with stock torch ops."""
+        from . import ops
+        k = ops.check_top_k(k)
+        dev = self.embed_user_GMF.weight.device
+        u = torch.as_tensor(users)
+        cands = ops.candidate_lists(candidates, n_users=u.numel(), device=dev)
+        if dev.type == "cuda":
+            r = ops.rank_candidates(self, u, cands, k)
+            return ops.Ranked(r.items.to(torch.int64), r.slots.to(torch.int64), r.scores)
+        return self._rank_cpu(u, cands, k)
+
+    @torch.no_grad()
+    def _rank_cpu(self, users, cands, k, chunk_pairs=1 << 20):
+        from . import ops
+        u = users.to(torch.int64)
+        ptr = torch.as_tensor(cands.ptr)
+        n, _ = ops.check_rank_args(u, ops.CandidateLists(ptr, cands.items), self.user_num, self.item_num)
+        c = cands.items.to(torch.int64)
+        out_i = torch.full((n, k), -1, dtype=torch.int64)
+        out_j = torch.full((n, k), -1, dtype=torch.int64)
+        out_s = torch.full((n, k), float("-inf"), dtype=torch.float32)
+        lens = ptr[1:] - ptr[:-1]
+        width = int(lens.max()) if n else 0
+        if width == 0:
+            return ops.Ranked(out_i, out_j, out_s)
+        m = min(k, width)
+        step = max(1, chunk_pairs // width)
+        for b in range(0, n, step):
+            e = min(n, b + step)
+            ln = lens[b:e]
+            lo, hi = int(ptr[b]), int(ptr[e])
+            z = self._logits_eval(u[b:e].repeat_interleave(ln), c[lo:hi])
+            col = torch.arange(width).unsqueeze(0)
+            inside = col < ln.unsqueeze(1)  # [lists, width], row-major = the flat order
+            s = torch.full(inside.shape, float("-inf"), dtype=torch.float32)
+            ids = torch.full(inside.shape, -1, dtype=torch.int64)
+            s[inside] = z
+            ids[inside] = c[lo:hi]
+            # stable: equal scores keep ascending slots; the padding sorts last
+            val, idx = torch.sort(s, dim=1, descending=True, stable=True)
+            keep = inside[:, :m]  # entry r exists when r < len
+            out_i[b:e, :m] = torch.where(keep, ids.gather(1, idx[:, :m]), torch.full_like(idx[:, :m], -1))
+            out_j[b:e, :m] = torch.where(keep, idx[:, :m], torch.full_like(idx[:, :m], -1))
+            out_s[b:e, :m] = torch.where(keep, val[:, :m], torch.full_like(val[:, :m], float("-inf")))
+        return ops.Ranked(out_i, out_j, out_s)
+
     # ---------------------------------------------------------------- neighbours
     def similar_items(self, items, k=10, space=None, metric="cosine", exclude_self=True):
         """The k items whose learned embedding is most similar to each queried item's:

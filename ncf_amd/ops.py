@@ -718,6 +718,119 @@ def select_negatives(model, users, candidates):
 
 
 # ---------------------------------------------------------------------------
+# candidate ranking: top-K over caller-supplied item lists (ncf_rank_candidates; added within ABI 21)
+class CandidateLists(collections.namedtuple("CandidateLists", "ptr items")):
+    """Candidate lists of n queried users: ptr int64 [n + 1] (ascending, ptr[0] = 0,
+    ptr[n] = len(items)), items int32; user q's list is items[ptr[q] .. ptr[q + 1]), and a
+    candidate's slot is its position inside its own list."""
+    __slots__ = ()
+
+
+class Ranked(collections.namedtuple("Ranked", "items slots scores")):
+    """Result of NCF.rank: per list the k best candidates' item ids, their slots in the list
+    and their logits, [n, k] each; -1 / -1 / -inf beyond the list's length."""
+    __slots__ = ()
+
+
+def candidate_lists(lists, n_users=None, device=None):
+    """CandidateLists from a CandidateLists (returned as it is), a sequence of per-user id
+    sequences (ragged), a 2-D [n, m] array (one fixed-length list per row) or a 1-D array
+    (one shared list for each of the `n_users` queried users).  ValueError for any other shape."""
+    if isinstance(lists, CandidateLists):
+        return lists
+    dev = torch.device("cpu") if device is None else torch.device(device)
+    if isinstance(lists, (list, tuple)) and any(np.ndim(x) > 0 or isinstance(x, (list, tuple)) for x in lists):
+        rows = [np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x).reshape(-1) for x in lists]
+        ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in rows], out=ptr[1:])
+        flat = np.concatenate(rows) if rows else np.zeros(0)
+        return CandidateLists(torch.from_numpy(ptr).to(dev), torch.from_numpy(flat.astype(np.int64)).to(dev))
+    c = torch.as_tensor(lists)
+    if c.dim() == 2:
+        n, m = c.shape
+        ptr = torch.arange(n + 1, dtype=torch.int64) * m
+        return CandidateLists(ptr.to(dev), c.reshape(-1).to(dev))
+    if c.dim() == 1:
+        if n_users is None:
+            raise ValueError("candidate_lists: a shared 1-D list needs n_users")
+        n, m = int(n_users), c.numel()
+        ptr = torch.arange(n + 1, dtype=torch.int64) * m
+        return CandidateLists(ptr.to(dev), c.repeat(n).to(dev))
+    raise ValueError("candidates: a CandidateLists, a sequence of lists, a 2-D [n, m] array or a 1-D shared list")
+
+
+def check_rank_args(users, cands, user_num, item_num):
+    """(n_lists, n_cand) of users [n] and a CandidateLists: ValueError for a bad shape or dtype, a
+    non-monotone ptr or a users / ptr length mismatch, IndexError for an id outside the tables."""
+    if users.dim() != 1:
+        raise ValueError("rank: users [n]")
+    n = int(users.numel())
+    ptr, items = cands.ptr, cands.items
+    if ptr.dim() != 1 or items.dim() != 1 or ptr.dtype != torch.int64 or items.dtype.is_floating_point:
+        raise ValueError("rank: CandidateLists needs ptr int64 [n + 1] and integer items")
+    if ptr.numel() != n + 1:
+        raise ValueError(f"rank: {n} users but ptr has {ptr.numel()} entries (n + 1 expected)")
+    first, last = ptr[[0, -1]].tolist()
+    if first != 0 or last != items.numel() or (n and bool((ptr[1:] < ptr[:-1]).any())):
+        raise ValueError("rank: ptr must ascend from 0 to len(items)")
+    if n and (int(users.min()) < 0 or int(users.max()) >= user_num):
+        raise IndexError("index out of range in self (user id)")
+    if items.numel() and (int(items.min()) < 0 or int(items.max()) >= item_num):
+        raise IndexError("index out of range in self (item id)")
+    return n, int(items.numel())
+
+
+@contextlib.contextmanager
+def _rank_materialised():
+    """Tests: ncf_rank_candidates through its materialised path whatever the shape."""
+    L.check(L.hip().ncf_debug_set_rank_path(L.PATH_LAYERED), "ncf_debug_set_rank_path")
+    try:
+        yield
+    finally:
+        L.hip().ncf_debug_set_rank_path(0)
+
+
+def rank_workspace(lay, n_lists, n_cand, k, owner, dev):
+    need = int(L.hip().ncf_rank_candidates_workspace_bytes(L.ctypes.byref(lay), int(n_lists), int(n_cand), int(k)))
+    if need < 0:
+        raise ValueError("ncf_rank_candidates_workspace_bytes failed")
+    return _ws(owner, "_ncf_rank_ws", need, dev)
+
+
+def rank_into(flat, lay, users_i32, ptr_i64, cand_i32, k, items_out, slots_out, scores_out, ws):
+    """One ncf_rank_candidates call on the current stream into preallocated tensors
+    (capturable: nothing is allocated or synchronised).  users_i32 [n], ptr_i64 [n + 1],
+    cand_i32 [ptr[n]]; outputs [n, k]; slots_out may be None."""
+    L.check(L.hip().ncf_rank_candidates(L.ctypes.byref(lay), flat.data_ptr(), users_i32.data_ptr(),
+                                        ptr_i64.data_ptr(), cand_i32.data_ptr(), users_i32.numel(),
+                                        cand_i32.numel(), int(k), items_out.data_ptr(), L.ptr(slots_out),
+                                        scores_out.data_ptr(),
+                                        None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
+                                        L.stream_ptr(flat.device)), "ncf_rank_candidates")
+
+
+def rank_candidates(model, users, cands, k):
+    """Ranked (items int32 [n, k], slots int32 [n, k], scores float32 [n, k]) of a HIP-resident
+    model: the k best candidates of every list, score descending then slot ascending."""
+    k = check_top_k(k)
+    flat, lay = ensure_flat(model)
+    dev = flat.device
+    u = _as_i32(users, dev)
+    cands = candidate_lists(cands, n_users=u.numel(), device=dev)
+    ptr = torch.as_tensor(cands.ptr, device=dev).contiguous()
+    n, n_cand = check_rank_args(u, CandidateLists(ptr, cands.items), model.user_num, model.item_num)
+    c = _as_i32(cands.items, dev)
+    items = torch.empty((n, k), dtype=torch.int32, device=dev)
+    slots = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    if n == 0:
+        return Ranked(items, slots, scores)
+    ws = rank_workspace(lay, n, n_cand, k, model, dev)
+    rank_into(flat, lay, u, ptr, c, k, items, slots, scores, ws)
+    return Ranked(items, slots, scores)
+
+
+# ---------------------------------------------------------------------------
 # fold-in: vectors for unseen users from their interaction lists (ncf_fold_in; added within ABI 21)
 class FoldExamples(collections.namedtuple("FoldExamples", "ptr items labels")):
     """Examples of Q folded users: ptr int64 [Q + 1], items int32 [E], labels float32 [E]

@@ -48,6 +48,9 @@ __host__ __device__ __forceinline__ uint32_t dropout_hash(uint32_t seed, uint32_
 // score descending, then id ascending (a total order), one wave per list.
 namespace ncf {
 
+// Workspace layouts: every piece starts on a 256-byte boundary
+inline int64_t ws_align(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+
 constexpr int RC_WAVES = 4;
 constexpr int RC_MAXK = 128;
 constexpr int RC_IDMAX = 0x7fffffff;  // id of an empty list slot (sorts last)
@@ -124,6 +127,15 @@ __global__ __launch_bounds__(NW * 64) void rc_merge_kernel(const float* __restri
         items_out[q * K + j] = id == RC_IDMAX ? -1 : id;
         scores_out[q * K + j] = ls[j];
     }
+}
+
+// rc_merge_kernel over nq queries on stream st (launch only: the caller checks launch_status).
+// A template for the reason rc_merge_kernel is one.
+template <int NW = RC_WAVES>
+void launch_merge(const float* part_s, const int32_t* part_i, int64_t nq, int nsplit, int K, int32_t* ids_out,
+                  float* scores_out, hipStream_t st) {
+    hipLaunchKernelGGL(rc_merge_kernel<NW>, dim3((unsigned)((nq + NW - 1) / NW)), dim3(NW * 64),
+                       (size_t)NW * 2 * K * 4, st, part_s, part_i, nq, nsplit, K, ids_out, scores_out);
 }
 
 }  // namespace ncf

@@ -655,11 +655,7 @@ using namespace ncf;
 
 extern "C" {
 
-int ncf_debug_set_fold_path(int path) {
-    if (path != 0 && path != NCF_PATH_LAYERED) return NCF_E_ARG;
-    g_fold_path = path;
-    return NCF_OK;
-}
+int ncf_debug_set_fold_path(int path) { return set_debug_path(&g_fold_path, path); }
 
 int64_t ncf_fold_in_workspace_bytes(const ncf_layout* lay, int64_t n_users, int64_t n_examples, int steps) {
     if (!lay || n_users < 0 || n_examples < 0 || steps < 1 || lay->item_num <= 0) return -1;

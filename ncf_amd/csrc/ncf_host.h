@@ -17,11 +17,26 @@ int ensure_lds(const void* fn, int64_t bytes);  // hipFuncSetAttribute once per 
 Ranges make_ranges(const int64_t* ranges, int nranges, int* err);
 int diag_flags();  // ncf_debug_set_diag's value
 
-// Workspace layouts: every piece starts on a 256-byte boundary
-inline int64_t ws_align(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+// ncf_debug_set_*_path of a serving entry point: *g = 0 (by shape) or NCF_PATH_LAYERED
+inline int set_debug_path(int* g, int path) {
+    if (path != 0 && path != NCF_PATH_LAYERED) return NCF_E_ARG;
+    *g = path;
+    return NCF_OK;
+}
 
-// Materialised paths (ncf_recommend, ncf_select_negatives): packed rows, their logits and
-// ncf_forward's own workspace for chunks of at most `pairs` (user, item) pairs.
+// Rows of Pu / Ag where a fused kernel gathers them per pair: the call's n rows when they are
+// fewer than the users (by_row: row = the call's row), else the user table (row = user id).
+struct UserRows {
+    int64_t R;
+    int by_row;
+};
+inline UserRows serve_user_rows(const ncf_layout* lay, int64_t n) {
+    return n < lay->user_num ? UserRows{n, 1} : UserRows{(int64_t)lay->user_num, 0};
+}
+
+// Materialised paths (ncf_recommend, ncf_select_negatives, ncf_rank_candidates): packed rows,
+// their logits and ncf_forward's own workspace for chunks of at most `pairs` (user, item)
+// pairs.  (ws_align is in ncf_common.h, the fused paths' proj_ws in ncf_tower_tile.h.)
 struct MatWs {
     int64_t rows, logits, fwd, fwd_bytes, total;
 };
@@ -35,18 +50,25 @@ inline MatWs mat_ws(const ncf_layout* lay, int64_t pairs) {
     return w;
 }
 
-// Fused paths: the layer-0 projections Pi [item_num][kp0], Pu [user_rows][kp0] and
-// Ag [user_rows][fp] (rc_proj_kernel, ncf_tower_tile.h); total = the first byte after them.
-struct ProjWs {
-    int64_t pi, pu, ag, total;
-};
-inline ProjWs proj_ws(const ncf_layout* lay, int64_t user_rows, int kp0, int fp) {
-    ProjWs w;
-    w.pi = 0;
-    w.pu = ws_align((int64_t)lay->item_num * kp0 * 4);
-    w.ag = w.pu + ws_align(user_rows * kp0 * 4);
-    w.total = w.ag + ws_align(user_rows * fp * 4);
-    return w;
+// The materialised loop over [0, total) in chunks [b, b + c) of at most `chunk` units:
+// make_rows(b, c, rows) launches the rows kernel and returns its pair count, ncf_forward scores
+// them -- into the workspace's logit buffer, reused, or with all_logits (units = pairs) into
+// all_logits + b -- and consume(b, c, those logits) launches their reader.  The first
+// ncf_forward failure, else NCF_OK (the caller ends with launch_status).
+template <class MakeRows, class Consume>
+int mat_run(const ncf_layout* lay, const float* params, const MatWs& W, char* ws, float* all_logits, int64_t total,
+            int64_t chunk, void* stream, MakeRows make_rows, Consume consume) {
+    uint64_t* rows = reinterpret_cast<uint64_t*>(ws + W.rows);
+    void* fws = W.fwd_bytes ? ws + W.fwd : nullptr;
+    for (int64_t b = 0; b < total; b += chunk) {
+        const int64_t c = total - b < chunk ? total - b : chunk;
+        const int64_t pairs = make_rows(b, c, rows);
+        float* lg = all_logits ? all_logits + b : reinterpret_cast<float*>(ws + W.logits);
+        const int rc = ncf_forward(lay, params, rows, pairs, lg, fws, W.fwd_bytes, stream);
+        if (rc != NCF_OK) return rc;
+        consume(b, c, lg);
+    }
+    return NCF_OK;
 }
 
 // ncf_step.hip: layout geometry

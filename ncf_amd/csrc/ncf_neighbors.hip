@@ -314,9 +314,7 @@ int ncf_neighbors(const ncf_layout* lay, const float* params, int side, int spac
     hipStream_t st = (hipStream_t)stream;
     if (a.cosine) hipLaunchKernelGGL(nb_norm_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
     hipLaunchKernelGGL(nb_kernel, dim3((unsigned)G.tiles, (unsigned)G.nsplit), dim3(RC_WAVES * 64), (size_t)lds, st, a);
-    hipLaunchKernelGGL(rc_merge_kernel<>, dim3((unsigned)((n_queries + RC_WAVES - 1) / RC_WAVES)), dim3(RC_WAVES * 64),
-                       (size_t)RC_WAVES * 2 * K * 4, st, a.part_s, a.part_i, n_queries, G.nsplit, K, ids_out,
-                       scores_out);
+    launch_merge(a.part_s, a.part_i, n_queries, G.nsplit, K, ids_out, scores_out, st);
     return launch_status();
 }
 

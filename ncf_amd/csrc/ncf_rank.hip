@@ -220,9 +220,6 @@ struct RankKernel {
 };
 static const TileEntry* rk_fused(const ncf_layout* lay) { return tile_fused<RankKernel>(lay, g_rk_path); }
 
-// Rows of Pu / Ag: the call's rows when they are fewer than the users, else the user table.
-static int64_t rk_user_rows(const ncf_layout* lay, int64_t nq) { return nq < lay->user_num ? nq : lay->user_num; }
-
 // Splits of every list's tiles over grid.y, from the number of lists alone.
 static int rk_splits(int64_t nq) {
     if (nq >= RK_FILL_LISTS) return 1;
@@ -239,7 +236,7 @@ struct RkFusedWs {
 static RkFusedWs rk_fused_ws(const TileEntry* e, const ncf_layout* lay, int64_t nq, int K) {
     RkFusedWs w;
     const int nsplit = rk_splits(nq);
-    w.p = proj_ws(lay, rk_user_rows(lay, nq), e->kp0, e->fp);
+    w.p = proj_ws(lay, serve_user_rows(lay, nq).R, e->kp0, e->fp);
     const int64_t part = nsplit > 1 ? ws_align(nq * nsplit * K * 4) : 0;
     w.ps = w.p.total;
     w.pid = w.ps + part;
@@ -268,11 +265,7 @@ using namespace ncf;
 
 extern "C" {
 
-int ncf_debug_set_rank_path(int path) {
-    if (path != 0 && path != NCF_PATH_LAYERED) return NCF_E_ARG;
-    g_rk_path = path;
-    return NCF_OK;
-}
+int ncf_debug_set_rank_path(int path) { return set_debug_path(&g_rk_path, path); }
 
 int64_t ncf_rank_candidates_workspace_bytes(const ncf_layout* lay, int64_t n_lists, int64_t n_cand, int top_k) {
     if (!lay || n_lists < 0 || n_cand < 0 || top_k < 1 || top_k > RC_MAXK || lay->item_num <= 0 ||
@@ -300,7 +293,7 @@ int ncf_rank_candidates(const ncf_layout* lay, const float* params, const int32_
     const int K = top_k;
 
     if (const TileEntry* e = rk_fused(lay)) {
-        const int64_t R = rk_user_rows(lay, n_lists);
+        const UserRows ur = serve_user_rows(lay, n_lists);
         const RkFusedWs W = rk_fused_ws(e, lay, n_lists, K);
         const int nsplit = rk_splits(n_lists);
         RkArgs a;
@@ -312,19 +305,13 @@ int ncf_rank_candidates(const ncf_layout* lay, const float* params, const int32_
         a.cand = cand;
         a.nq = n_lists;
         a.K = K;
-        a.by_row = n_lists < lay->user_num ? 1 : 0;
-        a.Pi = reinterpret_cast<float*>(ws + W.p.pi);
-        a.Pu = reinterpret_cast<float*>(ws + W.p.pu);
-        a.Ag = reinterpret_cast<float*>(ws + W.p.ag);
+        a.by_row = ur.by_row;
         a.part_s = reinterpret_cast<float*>(ws + W.ps);
         a.part_i = reinterpret_cast<int32_t*>(ws + W.pid);
         a.items_out = items_out;
         a.slots_out = slots_out;
         a.scores_out = scores_out;
-        const int64_t nproj = ((int64_t)lay->item_num + R) * e->kp0 + R * e->fp;
-        hipLaunchKernelGGL(rc_proj_kernel<>, dim3((unsigned)((nproj + 255) / 256)), dim3(256), 0, st, *lay, params,
-                           a.by_row ? users : nullptr, R, e->kp0, e->fp, const_cast<float*>(a.Pi),
-                           const_cast<float*>(a.Pu), const_cast<float*>(a.Ag));
+        launch_proj(lay, params, ur.by_row ? users : nullptr, ur.R, e, ws, st, &a.Pi, &a.Pu, &a.Ag);
         const int64_t wgs = n_lists < RK_MAX_WG ? n_lists : RK_MAX_WG;
         void* args[] = {&a};
         if (hipLaunchKernel(e->fn, dim3((unsigned)wgs, (unsigned)nsplit), dim3(RC_WAVES * 64), args, 0, st) !=
@@ -333,9 +320,7 @@ int ncf_rank_candidates(const ncf_layout* lay, const float* params, const int32_
         if (nsplit > 1) {
             // the merged id key is the slot: into slots_out, or the workspace's array without one
             int32_t* slots = slots_out != nullptr ? slots_out : reinterpret_cast<int32_t*>(ws + W.slots);
-            hipLaunchKernelGGL(rc_merge_kernel<>, dim3((unsigned)((n_lists + RC_WAVES - 1) / RC_WAVES)),
-                               dim3(RC_WAVES * 64), (size_t)RC_WAVES * 2 * K * 4, st, a.part_s, a.part_i, n_lists,
-                               nsplit, K, slots, scores_out);
+            launch_merge(a.part_s, a.part_i, n_lists, nsplit, K, slots, scores_out, st);
             hipLaunchKernelGGL(rk_items_kernel, dim3((unsigned)((n_lists * K + 255) / 256)), dim3(256), 0, st,
                                cand_ptr, cand, slots, n_lists, K, items_out);
         }
@@ -343,16 +328,16 @@ int ncf_rank_candidates(const ncf_layout* lay, const float* params, const int32_
     }
 
     const RkMatWs W = rk_mat_ws(lay, n_cand);
-    uint64_t* rows = reinterpret_cast<uint64_t*>(ws + W.m.rows);
-    float* logits = reinterpret_cast<float*>(ws + W.all);
-    for (int64_t pb = 0; pb < n_cand; pb += W.chunk) {
-        const int64_t pc = n_cand - pb < W.chunk ? n_cand - pb : W.chunk;
-        hipLaunchKernelGGL(rk_rows_kernel, dim3((unsigned)((pc + 255) / 256)), dim3(256), 0, st, users, cand_ptr, cand,
-                           n_lists, pb, pc, rows);
-        const int rc = ncf_forward(lay, params, rows, pc, logits + pb, W.m.fwd_bytes ? ws + W.m.fwd : nullptr,
-                                   W.m.fwd_bytes, stream);
-        if (rc != NCF_OK) return rc;
-    }
+    float* logits = reinterpret_cast<float*>(ws + W.all);  // all n_cand of them: chunk pb writes logits + pb
+    const int rc = mat_run(
+        lay, params, W.m, ws, logits, n_cand, W.chunk, stream,
+        [&](int64_t pb, int64_t pc, uint64_t* rows) {
+            hipLaunchKernelGGL(rk_rows_kernel, dim3((unsigned)((pc + 255) / 256)), dim3(256), 0, st, users, cand_ptr,
+                               cand, n_lists, pb, pc, rows);
+            return pc;
+        },
+        [](int64_t, int64_t, const float*) {});  // the lists are selected once every chunk is scored
+    if (rc != NCF_OK) return rc;
     hipLaunchKernelGGL(rk_select_kernel, dim3((unsigned)((n_lists + RC_WAVES - 1) / RC_WAVES)), dim3(RC_WAVES * 64), 0,
                        st, logits, cand_ptr, cand, n_lists, K, items_out, slots_out, scores_out);
     return launch_status();

@@ -348,11 +348,7 @@ using namespace ncf;
 
 extern "C" {
 
-int ncf_debug_set_recommend_path(int path) {
-    if (path != 0 && path != NCF_PATH_LAYERED) return NCF_E_ARG;
-    g_rc_path = path;
-    return NCF_OK;
-}
+int ncf_debug_set_recommend_path(int path) { return set_debug_path(&g_rc_path, path); }
 
 int64_t ncf_recommend_workspace_bytes(const ncf_layout* lay, int64_t n_users, int top_k) {
     if (!lay || n_users < 0 || top_k < 1 || top_k > RC_MAXK || lay->item_num <= 0) return -1;
@@ -391,45 +387,36 @@ int ncf_recommend(const ncf_layout* lay, const float* params, const int32_t* use
         a.K = K;
         a.seen_ptr = seen_ptr;
         a.seen_items = seen_items;
-        a.Pi = reinterpret_cast<float*>(ws + W.p.pi);
-        a.Pu = reinterpret_cast<float*>(ws + W.p.pu);
-        a.Ag = reinterpret_cast<float*>(ws + W.p.ag);
         a.part_s = reinterpret_cast<float*>(ws + W.ps);
         a.part_i = reinterpret_cast<int32_t*>(ws + W.pid);
         a.nsplit = G.nsplit;
         a.cps = G.cps;
         a.upw = G.upw;
-        const int64_t nproj = ((int64_t)I + n_users) * e->kp0 + n_users * e->fp;
-        hipLaunchKernelGGL(rc_proj_kernel<>, dim3((unsigned)((nproj + 255) / 256)), dim3(256), 0, st, *lay, params,
-                           users, n_users, e->kp0, e->fp, const_cast<float*>(a.Pi), const_cast<float*>(a.Pu),
-                           const_cast<float*>(a.Ag));
+        launch_proj(lay, params, users, n_users, e, ws, st, &a.Pi, &a.Pu, &a.Ag);
         void* args[] = {&a};
         if (hipLaunchKernel(e->fn, dim3((unsigned)G.tiles, (unsigned)G.nsplit), dim3(RC_WAVES * 64), args, (size_t)lds,
                             st) != hipSuccess)
             return NCF_E_LAUNCH;
-        hipLaunchKernelGGL(rc_merge_kernel<>, dim3((unsigned)((n_users + RC_WAVES - 1) / RC_WAVES)), dim3(RC_WAVES * 64),
-                           (size_t)RC_WAVES * 2 * K * 4, st, a.part_s, a.part_i, n_users, G.nsplit, K, items_out,
-                           scores_out);
+        launch_merge(a.part_s, a.part_i, n_users, G.nsplit, K, items_out, scores_out, st);
         return launch_status();
     }
 
     const int64_t ucmax = rc_mat_users(lay, n_users);
     const MatWs W = mat_ws(lay, ucmax * I);
-    uint64_t* rows = reinterpret_cast<uint64_t*>(ws + W.rows);
-    float* logits = reinterpret_cast<float*>(ws + W.logits);
-    for (int64_t qb = 0; qb < n_users; qb += ucmax) {
-        const int64_t uc = n_users - qb < ucmax ? n_users - qb : ucmax;
-        const int64_t pairs = uc * I;
-        hipLaunchKernelGGL(rc_rows_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, users, qb, uc, I,
-                           rows);
-        const int rc = ncf_forward(lay, params, rows, pairs, logits, W.fwd_bytes ? ws + W.fwd : nullptr, W.fwd_bytes,
-                                   stream);
-        if (rc != NCF_OK) return rc;
-        hipLaunchKernelGGL(rc_select_kernel, dim3((unsigned)((uc + RC_WAVES - 1) / RC_WAVES)), dim3(RC_WAVES * 64),
-                           (size_t)RC_WAVES * (2 * K + 64) * 4, st, logits, users, qb, uc, I, K, seen_ptr, seen_items,
-                           items_out, scores_out);
-    }
-    return launch_status();
+    const int rc = mat_run(
+        lay, params, W, ws, nullptr, n_users, ucmax, stream,
+        [&](int64_t qb, int64_t uc, uint64_t* rows) {
+            const int64_t pairs = uc * I;
+            hipLaunchKernelGGL(rc_rows_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, users, qb, uc,
+                               I, rows);
+            return pairs;
+        },
+        [&](int64_t qb, int64_t uc, const float* logits) {
+            hipLaunchKernelGGL(rc_select_kernel, dim3((unsigned)((uc + RC_WAVES - 1) / RC_WAVES)),
+                               dim3(RC_WAVES * 64), (size_t)RC_WAVES * (2 * K + 64) * 4, st, logits, users, qb, uc, I,
+                               K, seen_ptr, seen_items, items_out, scores_out);
+        });
+    return rc != NCF_OK ? rc : launch_status();
 }
 
 int ncf_hr_ndcg(const float* logits, const int32_t* items, int64_t n, int batch, int top_k, int32_t* hr, float* ndcg,

@@ -181,9 +181,6 @@ struct SelKernel {
 };
 static const TileEntry* sel_fused(const ncf_layout* lay) { return tile_fused<SelKernel>(lay, g_sel_path); }
 
-// Rows of Pu / Ag: the call's rows when they are fewer than the users, else the user table.
-static int64_t sel_user_rows(const ncf_layout* lay, int64_t n) { return n < lay->user_num ? n : lay->user_num; }
-
 static int64_t sel_mat_groups(int64_t n, int m) {
     const int64_t gc = RC_MAT_PAIRS / m;  // m <= 64: at least 2,048 groups
     return gc < n ? gc : n;
@@ -195,18 +192,15 @@ using namespace ncf;
 
 extern "C" {
 
-int ncf_debug_set_select_path(int path) {
-    if (path != 0 && path != NCF_PATH_LAYERED) return NCF_E_ARG;
-    g_sel_path = path;
-    return NCF_OK;
-}
+int ncf_debug_set_select_path(int path) { return set_debug_path(&g_sel_path, path); }
 
 int64_t ncf_select_negatives_workspace_bytes(const ncf_layout* lay, int64_t n, int m) {
     if (!lay || n < 0 || m < 1 || m > SEL_MAXM || lay->item_num <= 0 || lay->user_num <= 0) return -1;
     if (!ncf_supported(lay->model_type, lay->factor_num, lay->num_layers)) return -1;
     if (n == 0) return 0;
     const TileEntry* e = sel_fused(lay);
-    return e ? proj_ws(lay, sel_user_rows(lay, n), e->kp0, e->fp).total : mat_ws(lay, sel_mat_groups(n, m) * m).total;
+    if (e) return proj_ws(lay, serve_user_rows(lay, n).R, e->kp0, e->fp).total;
+    return mat_ws(lay, sel_mat_groups(n, m) * m).total;
 }
 
 int ncf_select_negatives(const ncf_layout* lay, const float* params, const int32_t* users, const int32_t* cand,
@@ -222,8 +216,7 @@ int ncf_select_negatives(const ncf_layout* lay, const float* params, const int32
     char* ws = static_cast<char*>(workspace);
 
     if (const TileEntry* e = sel_fused(lay)) {
-        const int64_t R = sel_user_rows(lay, n);
-        const ProjWs W = proj_ws(lay, R, e->kp0, e->fp);
+        const UserRows ur = serve_user_rows(lay, n);
         SelArgs a;
         memset(&a, 0, sizeof(a));
         a.lay = *lay;
@@ -232,17 +225,11 @@ int ncf_select_negatives(const ncf_layout* lay, const float* params, const int32
         a.cand = cand;
         a.n = n;
         a.m = m;
-        a.by_row = n < lay->user_num ? 1 : 0;
-        a.Pi = reinterpret_cast<float*>(ws + W.pi);
-        a.Pu = reinterpret_cast<float*>(ws + W.pu);
-        a.Ag = reinterpret_cast<float*>(ws + W.ag);
+        a.by_row = ur.by_row;
         a.neg_out = neg_out;
         a.slot_out = slot_out;
         a.score_out = score_out;
-        const int64_t nproj = ((int64_t)lay->item_num + R) * e->kp0 + R * e->fp;
-        hipLaunchKernelGGL(rc_proj_kernel<>, dim3((unsigned)((nproj + 255) / 256)), dim3(256), 0, st, *lay, params,
-                           a.by_row ? users : nullptr, R, e->kp0, e->fp, const_cast<float*>(a.Pi),
-                           const_cast<float*>(a.Pu), const_cast<float*>(a.Ag));
+        launch_proj(lay, params, ur.by_row ? users : nullptr, ur.R, e, ws, st, &a.Pi, &a.Pu, &a.Ag);
         const int64_t units = m <= 16 ? (n + 16 / m - 1) / (16 / m) : n;
         int64_t wgs = (units + RC_WAVES - 1) / RC_WAVES;
         if (wgs > SEL_MAX_WG) wgs = SEL_MAX_WG;
@@ -254,20 +241,19 @@ int ncf_select_negatives(const ncf_layout* lay, const float* params, const int32
 
     const int64_t gcmax = sel_mat_groups(n, m);
     const MatWs W = mat_ws(lay, gcmax * m);
-    uint64_t* rows = reinterpret_cast<uint64_t*>(ws + W.rows);
-    float* logits = reinterpret_cast<float*>(ws + W.logits);
-    for (int64_t pb = 0; pb < n; pb += gcmax) {
-        const int64_t gc = n - pb < gcmax ? n - pb : gcmax;
-        const int64_t pairs = gc * m;
-        hipLaunchKernelGGL(sel_rows_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, users, cand, pb, gc,
-                           m, rows);
-        const int rc = ncf_forward(lay, params, rows, pairs, logits, W.fwd_bytes ? ws + W.fwd : nullptr, W.fwd_bytes,
-                                   stream);
-        if (rc != NCF_OK) return rc;
-        hipLaunchKernelGGL(sel_pick_kernel, dim3((unsigned)((gc + 255) / 256)), dim3(256), 0, st, logits, cand, pb, gc,
-                           m, neg_out, slot_out, score_out);
-    }
-    return launch_status();
+    const int rc = mat_run(
+        lay, params, W, ws, nullptr, n, gcmax, stream,
+        [&](int64_t pb, int64_t gc, uint64_t* rows) {
+            const int64_t pairs = gc * m;
+            hipLaunchKernelGGL(sel_rows_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, users, cand,
+                               pb, gc, m, rows);
+            return pairs;
+        },
+        [&](int64_t pb, int64_t gc, const float* logits) {
+            hipLaunchKernelGGL(sel_pick_kernel, dim3((unsigned)((gc + 255) / 256)), dim3(256), 0, st, logits, cand, pb,
+                               gc, m, neg_out, slot_out, score_out);
+        });
+    return rc != NCF_OK ? rc : launch_status();
 }
 
 }  // extern "C"

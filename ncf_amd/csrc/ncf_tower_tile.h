@@ -1,7 +1,8 @@
 // The in-register MFMA tower tile shared by the serving entry points -- ncf_recommend.hip
 // (full-catalogue top-K), ncf_select.hip (hardest negatives) and ncf_fold.hip (fold-in of
 // unseen users): the list of fused shapes and the table built from it, the padded shape
-// constants, the layer-0 projection prologue, the staging of the tower into LDS, and the
+// constants, the layer-0 projection prologue (its kernel, its place in a workspace and its
+// launch: rc_proj_kernel, proj_ws, launch_proj), the staging of the tower into LDS, and the
 // pair score (h0, the layer ladder, the predict and GMF dots, the logit).  ncf_train.hip
 // builds kernel_table from the same shape list.
 //
@@ -28,7 +29,7 @@
 namespace ncf {
 
 constexpr int RC_CH = 64;  // items per LDS chunk of ncf_recommend (one seen-mask bit per lane)
-// materialised paths (ncf_recommend, ncf_select_negatives): (user, item) pairs per chunk
+// materialised paths (ncf_recommend, ncf_select_negatives, ncf_rank_candidates): (user, item) pairs per chunk
 constexpr int64_t RC_MAT_PAIRS = 1 << 17;
 
 __host__ __device__ constexpr int rc_max(int a, int b) { return a > b ? a : b; }
@@ -148,6 +149,20 @@ __global__ __launch_bounds__(NT) void rc_proj_kernel(ncf_layout lay, const float
     else Ag[idx] = tile_ag(lay, prm, u, c);
 }
 
+// Where the projections lie in a workspace: Pi [item_num][kp0], Pu [user_rows][kp0] and
+// Ag [user_rows][fp]; total = the first byte after them.
+struct ProjWs {
+    int64_t pi, pu, ag, total;
+};
+inline ProjWs proj_ws(const ncf_layout* lay, int64_t user_rows, int kp0, int fp) {
+    ProjWs w;
+    w.pi = 0;
+    w.pu = ws_align((int64_t)lay->item_num * kp0 * 4);
+    w.ag = w.pu + ws_align(user_rows * kp0 * 4);
+    w.total = w.ag + ws_align(user_rows * fp * 4);
+    return w;
+}
+
 // ---------------------------------------------------------------------------
 // Tower weights W_1 .. W_NL zero padded in the layout rc_layer reads, the biases and the
 // predict weights of the tower output into LDS, by the NT threads of a workgroup.  No
@@ -255,6 +270,21 @@ const TileEntry* tile_fused(const ncf_layout* lay, int debug_path) {
     for (const TileEntry& e : table)
         if (e.mode == lay->model_type && e.F == lay->factor_num && e.L == Lk) return &e;
     return nullptr;
+}
+
+// rc_proj_kernel into the head of workspace ws (proj_ws) over R user rows: users[0 .. R), or
+// the user table with users == NULL; *Pi, *Pu, *Ag = where they lie.  Launch only: the caller
+// checks launch_status.  A template for the reason rc_proj_kernel is one.
+template <int NT = 256>
+void launch_proj(const ncf_layout* lay, const float* params, const int32_t* users, int64_t R, const TileEntry* e,
+                 char* ws, hipStream_t st, const float** Pi, const float** Pu, const float** Ag) {
+    const ProjWs W = proj_ws(lay, R, e->kp0, e->fp);
+    float *pi = reinterpret_cast<float*>(ws + W.pi), *pu = reinterpret_cast<float*>(ws + W.pu),
+          *ag = reinterpret_cast<float*>(ws + W.ag);
+    const int64_t nproj = ((int64_t)lay->item_num + R) * e->kp0 + R * e->fp;
+    hipLaunchKernelGGL(rc_proj_kernel<NT>, dim3((unsigned)((nproj + NT - 1) / NT)), dim3(NT), 0, st, *lay, params,
+                       users, R, e->kp0, e->fp, pi, pu, ag);
+    *Pi = pi, *Pu = pu, *Ag = ag;
 }
 
 }  // namespace ncf

@@ -12,14 +12,18 @@ Mirrors reference ``src/ncf/models.py``:
                                no silent fallback to ATen ops on the GPU.  On a CPU
                                device the module evaluates with stock torch CPU ops,
                                i.e. it behaves like the reference module it replaces.
+
+Everything served beyond ``forward`` (recommend, rank, ..., fold_in) is ``serving.ServingMixin``.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
+from .serving import ServingMixin
 
-class NCF(nn.Module):
+
+class NCF(ServingMixin, nn.Module):
     def __init__(self, user_num, item_num, factor_num, num_layers, dropout, model_type):
         super().__init__()
         self.model_type = model_type
@@ -135,370 +139,3 @@ class NCF(nn.Module):
             mlp = self.MLP_layers(torch.cat((self.embed_user_MLP(user), self.embed_item_MLP(item)), -1))
             output = torch.cat((gmf, mlp), -1)
         return self.predict_layer(output).view(-1)
-
-    # ---------------------------------------------------------------- recommend
-    def recommend(self, users, k=10, exclude=None):
-        """The k best items of every queried user over the whole catalogue:
-        ``(items int64 [Q, k], scores float32 [Q, k])`` on the model's device.  Scores
-        are ``forward(u, i)`` in eval mode (dropout never applies, whatever
-        ``self.training``); order: score descending, then item id ascending.
-        ``exclude``: items to leave out per user -- an ``ops.SeenCSR``
-        (``ops.seen_csr``), the DOK ``train_mat`` of ``load_all`` or a
-        ``(users, items)`` pair of arrays.  A user with fewer than k eligible items
-        gets item -1 and score -inf in the trailing slots.  1 <= k <= 128.
-
-        On a HIP device this is ``ncf_recommend`` (the fused score-and-select kernel);
-        a CPU model runs the same contract with stock torch ops."""
-        from . import ops
-        k = ops.check_top_k(k)
-        dev = self.embed_user_GMF.weight.device
-        seen = ops.as_seen(exclude, self, dev)
-        if dev.type == "cuda":
-            items, scores = ops.recommend(self, users, k, seen)
-            return items.to(torch.int64), scores
-        return self._recommend_cpu(users, k, seen)
-
-    def _logits_eval(self, user, item):
-        """forward() with the tower's Dropout modules skipped (eval semantics)."""
-        def tower(x):
-            for lin in self.linear_layers():
-                x = torch.relu(lin(x))
-            return x
-        if self.model_type == "GMF":
-            output = self.embed_user_GMF(user) * self.embed_item_GMF(item)
-        elif self.model_type == "MLP":
-            output = tower(torch.cat((self.embed_user_MLP(user), self.embed_item_MLP(item)), -1))
-        else:
-            gmf = self.embed_user_GMF(user) * self.embed_item_GMF(item)
-            mlp = tower(torch.cat((self.embed_user_MLP(user), self.embed_item_MLP(item)), -1))
-            output = torch.cat((gmf, mlp), -1)
-        return self.predict_layer(output).view(-1)
-
-    @torch.no_grad()
-    def _recommend_cpu(self, users, k, seen, chunk_pairs=1 << 20):
-        u = torch.as_tensor(users).to(torch.int64).view(-1)
-        if u.numel() and (int(u.min()) < 0 or int(u.max()) >= self.user_num):
-            raise IndexError("index out of range in self (user id)")
-        n_items = self.item_num
-        q = u.numel()
-        out_i = torch.full((q, k), -1, dtype=torch.int64)
-        out_s = torch.full((q, k), float("-inf"), dtype=torch.float32)
-        all_items = torch.arange(n_items, dtype=torch.int64)
-        step = max(1, chunk_pairs // n_items)
-        for b in range(0, q, step):
-            uc = u[b:b + step]
-            c = uc.numel()
-            s = self._logits_eval(uc.repeat_interleave(n_items), all_items.repeat(c)).view(c, n_items)
-            eligible = torch.full((c,), n_items, dtype=torch.int64)
-            if seen is not None:
-                lo, hi = seen.ptr[uc], seen.ptr[uc + 1]
-                eligible -= hi - lo
-                for r in range(c):
-                    s[r, seen.items[int(lo[r]):int(hi[r])].to(torch.int64)] = float("-inf")
-            # stable: equal scores keep ascending item ids; excluded items sort last
-            val, idx = torch.sort(s, dim=1, descending=True, stable=True)
-            m = min(k, n_items)
-            keep = torch.arange(m).unsqueeze(0) < eligible.unsqueeze(1)
-            out_i[b:b + c, :m] = torch.where(keep, idx[:, :m], torch.full_like(idx[:, :m], -1))
-            out_s[b:b + c, :m] = torch.where(keep, val[:, :m], torch.full_like(val[:, :m], float("-inf")))
-        return out_i, out_s
-
-    # ---------------------------------------------------------- hardest negatives
-    def hardest_negatives(self, users, candidates):
-        """Dynamic negative sampling: for every row, the candidate the model currently
-        scores highest.  ``users`` [n], ``candidates`` [n, m] (1 <= m <= 64; duplicate ids
-        inside a row are fine) -> ``ops.HardNegatives(items int64 [n], slots int64 [n],
-        scores float32 [n])`` on the model's device: the chosen item, its column in the
-        row and its score.  Scores are ``forward(u, i)`` in eval mode (dropout never
-        applies, whatever ``self.training``); equal scores resolve to the lowest column.
-        A row's result depends on that row alone.  IndexError for an id outside the
-        tables, ValueError for a bad m or shape.
-
-        On a HIP device this is ``ncf_select_negatives`` (the fused score-and-select
-        kernel); a CPU model runs the same contract with stock torch ops."""
-        from . import ops
-        if self.embed_user_GMF.weight.is_cuda:
-            r = ops.select_negatives(self, users, candidates)
-            return ops.HardNegatives(r.items.to(torch.int64), r.slots.to(torch.int64), r.scores)
-        return self._hardest_cpu(users, candidates)
-
-    @torch.no_grad()
-    def _hardest_cpu(self, users, candidates):
-        from . import ops
-        u = torch.as_tensor(users).to(torch.int64)
-        c = torch.as_tensor(candidates).to(torch.int64)
-        n, m = ops.check_candidate_shape(u, c)
-        if n and (int(u.min()) < 0 or int(u.max()) >= self.user_num):
-            raise IndexError("index out of range in self (user id)")
-        if n and (int(c.min()) < 0 or int(c.max()) >= self.item_num):
-            raise IndexError("index out of range in self (item id)")
-        if n == 0:
-            return ops.HardNegatives(c.new_zeros(0), c.new_zeros(0), torch.zeros(0))
-        s = self._logits_eval(u.repeat_interleave(m), c.reshape(-1)).view(n, m)
-        best = s.max(dim=1, keepdim=True).values
-        slots = (s == best).to(torch.int64).argmax(dim=1)  # the first column holding the maximum
-        rows = torch.arange(n)
-        return ops.HardNegatives(c[rows, slots], slots, s[rows, slots])
-
-    # ------------------------------------------------------------------- ranking
-    def rank(self, users, candidates, k=10):
-        """The k best of a caller-supplied item list per queried user (the second stage of a
-        recommender: re-rank a retriever's candidates, rank the items in stock):
-        ``ops.Ranked(items int64 [n, k], slots int64 [n, k], scores float32 [n, k])`` on the
-        model's device.  ``users`` [n]; ``candidates`` is an ``ops.CandidateLists``
-        (``ops.candidate_lists`` builds one from ragged lists), a 2-D ``[n, m]`` array (one
-        fixed-length list per row) or a 1-D array (one shared list for every queried user).
-        Scores are ``forward(u, i)`` in eval mode (dropout never applies, whatever
-        ``self.training``); order: score descending, then slot -- the candidate's position
-        in its own list -- ascending.  Duplicate ids inside a list are fine: every
-        occurrence is its own entry.  A list shorter than k gets item -1, slot -1 and score
-        -inf in the trailing entries.  A list's result depends on that list alone.
-        1 <= k <= 128.  IndexError for an id outside the tables; ValueError for a bad k or
-        shape, a non-monotone ``ptr`` or a ``users`` / ``ptr`` length mismatch.
-
-        On a HIP device this is ``ncf_rank_candidates`` (the fused score-and-select
-        kernel); a CPU model runs the same contract with stock torch ops."""
-        from . import ops
-        k = ops.check_top_k(k)
-        dev = self.embed_user_GMF.weight.device
-        u = torch.as_tensor(users)
-        cands = ops.candidate_lists(candidates, n_users=u.numel(), device=dev)
-        if dev.type == "cuda":
-            r = ops.rank_candidates(self, u, cands, k)
-            return ops.Ranked(r.items.to(torch.int64), r.slots.to(torch.int64), r.scores)
-        return self._rank_cpu(u, cands, k)
-
-    @torch.no_grad()
-    def _rank_cpu(self, users, cands, k, chunk_pairs=1 << 20):
-        from . import ops
-        u = users.to(torch.int64)
-        ptr = torch.as_tensor(cands.ptr)
-        n, _ = ops.check_rank_args(u, ops.CandidateLists(ptr, cands.items), self.user_num, self.item_num)
-        c = cands.items.to(torch.int64)
-        out_i = torch.full((n, k), -1, dtype=torch.int64)
-        out_j = torch.full((n, k), -1, dtype=torch.int64)
-        out_s = torch.full((n, k), float("-inf"), dtype=torch.float32)
-        lens = ptr[1:] - ptr[:-1]
-        width = int(lens.max()) if n else 0
-        if width == 0:
-            return ops.Ranked(out_i, out_j, out_s)
-        m = min(k, width)
-        step = max(1, chunk_pairs // width)
-        for b in range(0, n, step):
-            e = min(n, b + step)
-            ln = lens[b:e]
-            lo, hi = int(ptr[b]), int(ptr[e])
-            z = self._logits_eval(u[b:e].repeat_interleave(ln), c[lo:hi])
-            col = torch.arange(width).unsqueeze(0)
-            inside = col < ln.unsqueeze(1)  # [lists, width], row-major = the flat order
-            s = torch.full(inside.shape, float("-inf"), dtype=torch.float32)
-            ids = torch.full(inside.shape, -1, dtype=torch.int64)
-            s[inside] = z
-            ids[inside] = c[lo:hi]
-            # stable: equal scores keep ascending slots; the padding sorts last
-            val, idx = torch.sort(s, dim=1, descending=True, stable=True)
-            keep = inside[:, :m]  # entry r exists when r < len
-            out_i[b:e, :m] = torch.where(keep, ids.gather(1, idx[:, :m]), torch.full_like(idx[:, :m], -1))
-            out_j[b:e, :m] = torch.where(keep, idx[:, :m], torch.full_like(idx[:, :m], -1))
-            out_s[b:e, :m] = torch.where(keep, val[:, :m], torch.full_like(val[:, :m], float("-inf")))
-        return ops.Ranked(out_i, out_j, out_s)
-
-    # ---------------------------------------------------------------- neighbours
-    def similar_items(self, items, k=10, space=None, metric="cosine", exclude_self=True):
-        """The k items whose learned embedding is most similar to each queried item's:
-        ``(ids int64 [Q, k], scores float32 [Q, k])`` on the model's device.  Order:
-        score descending, then id ascending.  ``space``: ``"gmf"`` (rows of
-        ``embed_item_GMF``), ``"mlp"`` (rows of ``embed_item_MLP``) or ``"concat"``;
-        ``None`` is the model's own -- ``"gmf"`` for GMF, ``"mlp"`` for MLP, ``"concat"``
-        for NeuMF-end / NeuMF-pre.  All three exist for every model type (the four
-        tables always do), but a table the model type does not train stays at its
-        initialisation.  Concat is plain concatenation ``[GMF row | MLP row]`` under one
-        norm, so the wider MLP half weighs more.  ``metric``: ``"cosine"`` (a zero row
-        scores 0 against everything) or ``"dot"``.  ``exclude_self`` leaves the queried
-        id out of its own list.  With fewer than k eligible rows the trailing slots hold
-        id -1 and score -inf.  1 <= k <= 128.
-
-        On a HIP device this is ``ncf_neighbors`` (the fused score-and-select kernel);
-        a CPU model runs the same contract with stock torch ops."""
-        return self._similar("item", items, k, space, metric, exclude_self)
-
-    def similar_users(self, users, k=10, space=None, metric="cosine", exclude_self=True):
-        """``similar_items`` over the user tables (``embed_user_GMF`` / ``embed_user_MLP``)."""
-        return self._similar("user", users, k, space, metric, exclude_self)
-
-    def _similar(self, side, queries, k, space, metric, exclude_self):
-        from . import ops
-        k = ops.check_top_k(k)
-        ops.neighbor_codes(self.model_type, side, space, metric)  # ValueError for an unknown name
-        space = ops.default_space(self.model_type) if space is None else space
-        if self.embed_user_GMF.weight.is_cuda:
-            ids, scores = ops.neighbors(self, side, queries, k, space, metric, exclude_self)
-            return ids.to(torch.int64), scores
-        return self._neighbors_cpu(side, queries, k, space, metric, exclude_self)
-
-    @torch.no_grad()
-    def _neighbors_cpu(self, side, queries, k, space, metric, exclude_self, chunk_pairs=1 << 20):
-        gmf = (self.embed_item_GMF if side == "item" else self.embed_user_GMF).weight
-        mlp = (self.embed_item_MLP if side == "item" else self.embed_user_MLP).weight
-        table = {"gmf": gmf, "mlp": mlp}[space] if space != "concat" else torch.cat((gmf, mlp), 1)
-        table = table.detach().to(torch.float32)
-        n = table.shape[0]
-        qi = torch.as_tensor(queries).to(torch.int64).view(-1)
-        if qi.numel() and (int(qi.min()) < 0 or int(qi.max()) >= n):
-            raise IndexError(f"index out of range in self ({side} id)")
-        q = qi.numel()
-        out_i = torch.full((q, k), -1, dtype=torch.int64)
-        out_s = torch.full((q, k), float("-inf"), dtype=torch.float32)
-        if metric == "cosine":
-            ss = (table * table).sum(1)
-            inv = torch.where(ss > 0, 1.0 / torch.sqrt(ss), torch.zeros_like(ss))
-        m = min(k, n)
-        eligible = n - 1 if exclude_self else n
-        step = max(1, chunk_pairs // n)
-        for b in range(0, q, step):
-            ids = qi[b:b + step]
-            c = ids.numel()
-            s = table[ids] @ table.t()
-            if metric == "cosine":
-                s = s * inv[ids].unsqueeze(1) * inv.unsqueeze(0)
-            if exclude_self:
-                s[torch.arange(c), ids] = float("-inf")
-            # stable: equal scores keep ascending ids; the excluded id sorts last
-            val, idx = torch.sort(s, dim=1, descending=True, stable=True)
-            keep = (torch.arange(m) < eligible).unsqueeze(0).expand(c, m)
-            out_i[b:b + c, :m] = torch.where(keep, idx[:, :m], torch.full_like(idx[:, :m], -1))
-            out_s[b:b + c, :m] = torch.where(keep, val[:, :m], torch.full_like(val[:, :m], float("-inf")))
-        return out_i, out_s
-
-    # ------------------------------------------------------------------ fold-in
-    def fold_in(self, examples, steps=50, lr=0.01, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, init="mean",
-                state=None):
-        """Vectors for users that were not in the training set, fitted to their interaction
-        lists with everything else frozen: ``ops.FoldedUsers(gmf [Q, f], mlp [Q, dm],
-        loss [Q, steps], state)`` on the model's device.
-
-        ``examples``: an ``ops.FoldExamples`` (``ops.fold_examples`` builds one from
-        interaction lists with sampled negatives).  Per user, ``steps`` full-batch
-        ``torch.optim.Adam`` steps on its two vectors of the mean ``BCEWithLogits`` over its
-        examples of ``forward`` in eval mode (dropout never applies); ``weight_decay`` is
-        Adam's (added to the gradient).  A GMF model fits only ``gmf``, an MLP model only
-        ``mlp`` (the other half comes back as initialised).  ``loss[q, s]`` is the loss at
-        the vectors before step s's update; a user without examples has loss 0 and stays
-        where it started.  ``init``: ``"mean"`` (the column means of the user tables),
-        ``"zeros"`` or a ``(gmf, mlp)`` pair of start vectors.  ``state``: the
-        ``ops.FoldState`` of an earlier call to continue from (None: a fresh optimizer).
-        A user's result does not depend on the other users of the call.
-
-        On a HIP device this is ``ncf_fold_in`` (one kernel runs every step of a user);
-        a CPU model runs the same contract with stock torch autograd and
-        ``torch.optim.Adam``.  Serve the result with ``with_users``."""
-        from . import ops
-        steps = ops.check_fold_steps(steps)
-        ex = ops.check_fold_examples(examples, self.item_num)
-        q = ex.ptr.numel() - 1
-        gmf0, mlp0 = self._fold_init(init, q)
-        if self.embed_user_GMF.weight.is_cuda:
-            return ops.fold_in(self, ex, gmf0, mlp0, steps, lr, betas, eps, weight_decay, state)
-        return self._fold_in_cpu(ex, gmf0, mlp0, steps, lr, betas, eps, weight_decay, state)
-
-    def _fold_init(self, init, q):
-        ug, um = self.embed_user_GMF.weight.detach(), self.embed_user_MLP.weight.detach()
-        if isinstance(init, str):
-            if init == "mean":
-                return ug.mean(0, keepdim=True).repeat(q, 1), um.mean(0, keepdim=True).repeat(q, 1)
-            if init == "zeros":
-                return ug.new_zeros((q, ug.shape[1])), um.new_zeros((q, um.shape[1]))
-            raise ValueError(f"unknown init {init!r}: 'mean', 'zeros' or a (gmf, mlp) pair")
-        try:
-            g, m = init
-            g = torch.as_tensor(g, dtype=torch.float32).to(ug.device)
-            m = torch.as_tensor(m, dtype=torch.float32).to(ug.device)
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"unknown init {init!r}: 'mean', 'zeros' or a (gmf, mlp) pair") from e
-        if g.shape != (q, ug.shape[1]) or m.shape != (q, um.shape[1]):
-            raise ValueError("init: the start vectors must be gmf [Q, f] and mlp [Q, dm]")
-        return g, m
-
-    def _logits_vectors(self, ug, um, item):
-        """_logits_eval with the user rows given per example."""
-        def tower(x):
-            for lin in self.linear_layers():
-                x = torch.relu(lin(x))
-            return x
-        if self.model_type == "GMF":
-            output = ug * self.embed_item_GMF(item)
-        elif self.model_type == "MLP":
-            output = tower(torch.cat((um, self.embed_item_MLP(item)), -1))
-        else:
-            output = torch.cat((ug * self.embed_item_GMF(item),
-                                tower(torch.cat((um, self.embed_item_MLP(item)), -1))), -1)
-        return self.predict_layer(output).view(-1)
-
-    def _fold_in_cpu(self, ex, gmf0, mlp0, steps, lr, betas, eps, weight_decay, state):
-        from . import ops
-        q = ex.ptr.numel() - 1
-        f = gmf0.shape[1]
-        counts = (ex.ptr[1:] - ex.ptr[:-1])
-        owner = torch.repeat_interleave(torch.arange(q), counts)
-        weight = (1.0 / counts.clamp(min=1).to(torch.float32))[owner]
-        items = ex.items.to(torch.int64)
-        gmf = gmf0.detach().to(torch.float32).clone().requires_grad_(self.model_type != "MLP")
-        mlp = mlp0.detach().to(torch.float32).clone().requires_grad_(self.model_type != "GMF")
-        trained = [p for p in (gmf, mlp) if p.requires_grad]
-        opt = torch.optim.Adam(trained, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
-        width = f + mlp.shape[1]
-        m = torch.zeros((q, width)) if state is None else state.exp_avg.detach().to("cpu", torch.float32).clone()
-        v = torch.zeros((q, width)) if state is None else state.exp_avg_sq.detach().to("cpu", torch.float32).clone()
-        t0 = 0 if state is None else int(state.step)
-        if m.shape != (q, width) or v.shape != (q, width) or t0 < 0:
-            raise ValueError("fold-in state: exp_avg / exp_avg_sq must be [Q, f + dm] and step >= 0")
-        cols = {id(gmf): slice(0, f), id(mlp): slice(f, width)}
-        for p in trained:
-            opt.state[p] = {"step": torch.tensor(float(t0)), "exp_avg": m[:, cols[id(p)]].clone(),
-                            "exp_avg_sq": v[:, cols[id(p)]].clone()}
-        loss = torch.zeros((q, steps))
-        frozen = [(p, p.requires_grad) for p in self.parameters()]
-        for p, _ in frozen:
-            p.requires_grad_(False)
-        try:
-            for s in range(steps):
-                opt.zero_grad(set_to_none=True)
-                z = self._logits_vectors(gmf[owner], mlp[owner], items)
-                per = torch.nn.functional.binary_cross_entropy_with_logits(z, ex.labels, reduction="none") * weight
-                loss[:, s] = torch.zeros(q).index_add_(0, owner, per.detach())
-                if per.numel():
-                    per.sum().backward()
-                for p in trained:  # a call without examples still runs Adam with g = wd * p
-                    if p.grad is None:
-                        p.grad = torch.zeros_like(p)
-                opt.step()
-        finally:
-            for p, r in frozen:
-                p.requires_grad_(r)
-        for p in trained:
-            m[:, cols[id(p)]] = opt.state[p]["exp_avg"]
-            v[:, cols[id(p)]] = opt.state[p]["exp_avg_sq"]
-        return ops.FoldedUsers(gmf.detach(), mlp.detach(), loss, ops.FoldState(m, v, t0 + steps))
-
-    def with_users(self, folded):
-        """A new NCF of the same type and shape on the same device whose user tables are the
-        folded vectors (``user_num = Q``; ``folded``: an ``ops.FoldedUsers`` or a
-        ``(gmf, mlp)`` pair) and whose other parameters are copies of this model's, so
-        ``forward``, ``recommend``, ``similar_users`` and the evaluators serve folded users
-        as user ids 0 .. Q - 1."""
-        gmf, mlp = (folded.gmf, folded.mlp) if hasattr(folded, "gmf") else folded
-        ug, um = self.embed_user_GMF.weight, self.embed_user_MLP.weight
-        if gmf.dim() != 2 or mlp.dim() != 2 or gmf.shape[0] != mlp.shape[0] or gmf.shape[0] < 1 \
-                or gmf.shape[1] != ug.shape[1] or mlp.shape[1] != um.shape[1]:
-            raise ValueError("with_users: needs gmf [Q, f] and mlp [Q, dm] with Q >= 1")
-        with torch.random.fork_rng(devices=[]):  # the constructor's initialisation draws are discarded
-            new = NCF(gmf.shape[0], self.item_num, self.factor_num, self.num_layers, self.dropout, self.model_type)
-        new = new.to(ug.device)
-        with torch.no_grad():
-            for dst, src in zip(new.ordered_params()[:4], (gmf, self.embed_item_GMF.weight, mlp,
-                                                           self.embed_item_MLP.weight)):
-                dst.copy_(src.detach().to(dst.device))
-            for dst, src in zip(new.ordered_params()[4:], self.ordered_params()[4:]):
-                dst.copy_(src.detach())
-        new.train(self.training)
-        return new

@@ -303,6 +303,55 @@ def _ws(owner, attr, nbytes, dev):
     return ws
 
 
+def _ws_args(ws):
+    """(pointer, bytes) of a workspace tensor for the C ABI; None is a call that needs none."""
+    return (None, 0) if ws is None else (ws.data_ptr(), ws.numel() * 4)
+
+
+def _serve_ws(entry, attr, lay, owner, dev, *sizes):
+    """The workspace ncf_<entry>_workspace_bytes(lay, *sizes) asks for, cached on owner.<attr>."""
+    need = int(getattr(L.hip(), f"ncf_{entry}_workspace_bytes")(L.ctypes.byref(lay), *map(int, sizes)))
+    if need < 0:
+        raise ValueError(f"ncf_{entry}_workspace_bytes failed")
+    return _ws(owner, attr, need, dev)
+
+
+@contextlib.contextmanager
+def _forced_path(entry):
+    """ncf_debug_set_<entry>_path(PATH_LAYERED) for the block: that entry point's materialised
+    (ncf_fold_in: generic) path whatever the shape."""
+    setter = getattr(L.hip(), f"ncf_debug_set_{entry}_path")
+    L.check(setter(L.PATH_LAYERED), f"ncf_debug_set_{entry}_path")
+    try:
+        yield
+    finally:
+        setter(0)
+
+
+def check_id_range(*checks):
+    """IndexError, as nn.Embedding raises it, for the first (ids, bound, name) whose ids leave
+    [0, bound): "index out of range in self (<name> id)", without the suffix for name None.
+    The kernels do not bound-check their gathers.  Tensors on any device, empty ones pass; one
+    host read for the whole call."""
+    live = [c for c in checks if c[0].numel()]
+    if not live:
+        return
+    # with tensors on both sides the extremes meet on the HIP device: still one read
+    dev = next((t.device for t, _, _ in live if t.is_cuda), live[0][0].device)
+    lo_hi = torch.stack([f().to(dev, torch.int64) for t, _, _ in live for f in (t.min, t.max)]).tolist()
+    for (_, bound, name), lo, hi in zip(live, lo_hi[0::2], lo_hi[1::2]):
+        if lo < 0 or hi >= bound:
+            raise IndexError("index out of range in self" + (f" ({name} id)" if name else ""))
+
+
+def check_csr_ptr(ptr, n_entries, message):
+    """ValueError(message) unless ptr (at least one entry) starts at 0, ends at n_entries and
+    never descends; one host read."""
+    first, last, descends = torch.stack([ptr[0], ptr[-1], (ptr[1:] < ptr[:-1]).any().to(ptr.dtype)]).tolist()
+    if first != 0 or last != n_entries or descends:
+        raise ValueError(message)
+
+
 def forward_logits(flat, lay, rows, out=None, ws_owner=None):
     n = rows.numel()
     dev = flat.device
@@ -311,8 +360,7 @@ def forward_logits(flat, lay, rows, out=None, ws_owner=None):
     need = int(L.hip().ncf_forward_workspace_bytes(L.ctypes.byref(lay), n))
     ws = _ws(ws_owner if ws_owner is not None else _scratch, "_ncf_fwd_ws", need, dev)
     L.check(L.hip().ncf_forward(L.ctypes.byref(lay), flat.data_ptr(), rows.data_ptr(), n, out.data_ptr(),
-                                None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
-                                L.stream_ptr(dev)), "ncf_forward")
+                                *_ws_args(ws), L.stream_ptr(dev)), "ncf_forward")
     return out
 
 
@@ -440,12 +488,7 @@ def ncf_forward(model, user, item):
     i = _as_i32(item, dev).view(-1)
     if u.numel() != i.numel():
         raise ValueError("user and item must have the same number of elements")
-    if u.numel():
-        # nn.Embedding raises on an out-of-range id (models.py:98-103); the kernel
-        # does not bound-check its gathers, so check here (one host sync).
-        lo_hi = torch.stack([u.min(), u.max(), i.min(), i.max()]).tolist()
-        if lo_hi[0] < 0 or lo_hi[1] >= model.user_num or lo_hi[2] < 0 or lo_hi[3] >= model.item_num:
-            raise IndexError("index out of range in self")
+    check_id_range((u, model.user_num, None), (i, model.item_num, None))  # as nn.Embedding (models.py:98-103)
     rows = pack_rows(u, i)
     if torch.is_grad_enabled() and any(p.requires_grad for p in model.ordered_params()):
         return _NCFFunction.apply(rows, model, *model.ordered_params())
@@ -527,14 +570,9 @@ def check_top_k(k):
     return int(k)
 
 
-@contextlib.contextmanager
 def _recommend_materialised():
     """Tests: ncf_recommend through its materialised path whatever the shape."""
-    L.check(L.hip().ncf_debug_set_recommend_path(L.PATH_LAYERED), "ncf_debug_set_recommend_path")
-    try:
-        yield
-    finally:
-        L.hip().ncf_debug_set_recommend_path(0)
+    return _forced_path("recommend")
 
 
 def recommend_into(flat, lay, users_i32, k, seen, items_out, scores_out, ws):
@@ -544,16 +582,12 @@ def recommend_into(flat, lay, users_i32, k, seen, items_out, scores_out, ws):
     L.check(L.hip().ncf_recommend(L.ctypes.byref(lay), flat.data_ptr(), users_i32.data_ptr(), users_i32.numel(), k,
                                   None if seen is None else seen.ptr.data_ptr(),
                                   None if seen is None else seen.items.data_ptr(),
-                                  items_out.data_ptr(), scores_out.data_ptr(),
-                                  None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
-                                  L.stream_ptr(dev)), "ncf_recommend")
+                                  items_out.data_ptr(), scores_out.data_ptr(), *_ws_args(ws), L.stream_ptr(dev)),
+            "ncf_recommend")
 
 
 def recommend_workspace(lay, n_users, k, owner, dev):
-    need = int(L.hip().ncf_recommend_workspace_bytes(L.ctypes.byref(lay), int(n_users), int(k)))
-    if need < 0:
-        raise ValueError("ncf_recommend_workspace_bytes failed")
-    return _ws(owner, "_ncf_rec_ws", need, dev)
+    return _serve_ws("recommend", "_ncf_rec_ws", lay, owner, dev, n_users, k)
 
 
 def recommend(model, users, k, seen=None):
@@ -569,9 +603,7 @@ def recommend(model, users, k, seen=None):
     scores = torch.empty((q, k), dtype=torch.float32, device=dev)
     if q == 0:
         return items, scores
-    lo, hi = torch.stack([u.min(), u.max()]).tolist()
-    if lo < 0 or hi >= model.user_num:
-        raise IndexError("index out of range in self (user id)")
+    check_id_range((u, model.user_num, "user"))
     ws = recommend_workspace(lay, q, k, model, dev)
     recommend_into(flat, lay, u, k, seen, items, scores, ws)
     return items, scores
@@ -600,11 +632,7 @@ def neighbor_codes(model_type, side, space, metric):
 
 
 def neighbors_workspace(lay, side, space, n_queries, k, owner, dev):
-    need = int(L.hip().ncf_neighbors_workspace_bytes(L.ctypes.byref(lay), int(side), int(space), int(n_queries),
-                                                     int(k)))
-    if need < 0:
-        raise ValueError("ncf_neighbors_workspace_bytes failed")
-    return _ws(owner, "_ncf_nb_ws", need, dev)
+    return _serve_ws("neighbors", "_ncf_nb_ws", lay, owner, dev, side, space, n_queries, k)
 
 
 def neighbors_into(flat, lay, side, space, metric, q_i32, k, exclude_self, ids_out, scores_out, ws):
@@ -612,8 +640,7 @@ def neighbors_into(flat, lay, side, space, metric, q_i32, k, exclude_self, ids_o
     (capturable: nothing is allocated or synchronised)."""
     L.check(L.hip().ncf_neighbors(L.ctypes.byref(lay), flat.data_ptr(), int(side), int(space), int(metric),
                                   q_i32.data_ptr(), q_i32.numel(), int(k), 1 if exclude_self else 0,
-                                  ids_out.data_ptr(), scores_out.data_ptr(),
-                                  None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
+                                  ids_out.data_ptr(), scores_out.data_ptr(), *_ws_args(ws),
                                   L.stream_ptr(flat.device)), "ncf_neighbors")
 
 
@@ -632,9 +659,7 @@ def neighbors(model, side, queries, k, space=None, metric="cosine", exclude_self
     scores = torch.empty((n, k), dtype=torch.float32, device=dev)
     if n == 0:
         return ids, scores
-    lo, hi = torch.stack([q.min(), q.max()]).tolist()
-    if lo < 0 or hi >= (model.item_num if side == "item" else model.user_num):
-        raise IndexError(f"index out of range in self ({side} id)")
+    check_id_range((q, model.item_num if side == "item" else model.user_num, side))
     ws = neighbors_workspace(lay, side_c, space_c, n, k, model, dev)
     neighbors_into(flat, lay, side_c, space_c, metric_c, q, k, exclude_self, ids, scores, ws)
     return ids, scores
@@ -658,21 +683,13 @@ def check_candidates(m):
     return int(m)
 
 
-@contextlib.contextmanager
 def _select_materialised():
     """Tests: ncf_select_negatives through its materialised path whatever the shape."""
-    L.check(L.hip().ncf_debug_set_select_path(L.PATH_LAYERED), "ncf_debug_set_select_path")
-    try:
-        yield
-    finally:
-        L.hip().ncf_debug_set_select_path(0)
+    return _forced_path("select")
 
 
 def select_negatives_workspace(lay, n, m, owner, dev):
-    need = int(L.hip().ncf_select_negatives_workspace_bytes(L.ctypes.byref(lay), int(n), int(m)))
-    if need < 0:
-        raise ValueError("ncf_select_negatives_workspace_bytes failed")
-    return _ws(owner, "_ncf_sel_ws", need, dev)
+    return _serve_ws("select_negatives", "_ncf_sel_ws", lay, owner, dev, n, m)
 
 
 def select_negatives_into(flat, lay, users_i32, cand_i32, m, neg_out, slot_out, score_out, ws):
@@ -681,8 +698,7 @@ def select_negatives_into(flat, lay, users_i32, cand_i32, m, neg_out, slot_out, 
     (group p = cand[p * m .. p * m + m)); slot_out / score_out may be None."""
     L.check(L.hip().ncf_select_negatives(L.ctypes.byref(lay), flat.data_ptr(), users_i32.data_ptr(),
                                          cand_i32.data_ptr(), users_i32.numel(), int(m), neg_out.data_ptr(),
-                                         L.ptr(slot_out), L.ptr(score_out),
-                                         None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
+                                         L.ptr(slot_out), L.ptr(score_out), *_ws_args(ws),
                                          L.stream_ptr(flat.device)), "ncf_select_negatives")
 
 
@@ -707,11 +723,7 @@ def select_negatives(model, users, candidates):
     scores = torch.empty(n, dtype=torch.float32, device=dev)
     if n == 0:
         return HardNegatives(items, slots, scores)
-    lo_hi = torch.stack([u.min(), u.max(), c.min(), c.max()]).tolist()
-    if lo_hi[0] < 0 or lo_hi[1] >= model.user_num:
-        raise IndexError("index out of range in self (user id)")
-    if lo_hi[2] < 0 or lo_hi[3] >= model.item_num:
-        raise IndexError("index out of range in self (item id)")
+    check_id_range((u, model.user_num, "user"), (c, model.item_num, "item"))
     ws = select_negatives_workspace(lay, n, m, model, dev)
     select_negatives_into(flat, lay, u, c.view(-1), m, items, slots, scores, ws)
     return HardNegatives(items, slots, scores)
@@ -770,31 +782,18 @@ def check_rank_args(users, cands, user_num, item_num):
         raise ValueError("rank: CandidateLists needs ptr int64 [n + 1] and integer items")
     if ptr.numel() != n + 1:
         raise ValueError(f"rank: {n} users but ptr has {ptr.numel()} entries (n + 1 expected)")
-    first, last = ptr[[0, -1]].tolist()
-    if first != 0 or last != items.numel() or (n and bool((ptr[1:] < ptr[:-1]).any())):
-        raise ValueError("rank: ptr must ascend from 0 to len(items)")
-    if n and (int(users.min()) < 0 or int(users.max()) >= user_num):
-        raise IndexError("index out of range in self (user id)")
-    if items.numel() and (int(items.min()) < 0 or int(items.max()) >= item_num):
-        raise IndexError("index out of range in self (item id)")
+    check_csr_ptr(ptr, items.numel(), "rank: ptr must ascend from 0 to len(items)")
+    check_id_range((users, user_num, "user"), (items, item_num, "item"))
     return n, int(items.numel())
 
 
-@contextlib.contextmanager
 def _rank_materialised():
     """Tests: ncf_rank_candidates through its materialised path whatever the shape."""
-    L.check(L.hip().ncf_debug_set_rank_path(L.PATH_LAYERED), "ncf_debug_set_rank_path")
-    try:
-        yield
-    finally:
-        L.hip().ncf_debug_set_rank_path(0)
+    return _forced_path("rank")
 
 
 def rank_workspace(lay, n_lists, n_cand, k, owner, dev):
-    need = int(L.hip().ncf_rank_candidates_workspace_bytes(L.ctypes.byref(lay), int(n_lists), int(n_cand), int(k)))
-    if need < 0:
-        raise ValueError("ncf_rank_candidates_workspace_bytes failed")
-    return _ws(owner, "_ncf_rank_ws", need, dev)
+    return _serve_ws("rank_candidates", "_ncf_rank_ws", lay, owner, dev, n_lists, n_cand, k)
 
 
 def rank_into(flat, lay, users_i32, ptr_i64, cand_i32, k, items_out, slots_out, scores_out, ws):
@@ -804,9 +803,8 @@ def rank_into(flat, lay, users_i32, ptr_i64, cand_i32, k, items_out, slots_out, 
     L.check(L.hip().ncf_rank_candidates(L.ctypes.byref(lay), flat.data_ptr(), users_i32.data_ptr(),
                                         ptr_i64.data_ptr(), cand_i32.data_ptr(), users_i32.numel(),
                                         cand_i32.numel(), int(k), items_out.data_ptr(), L.ptr(slots_out),
-                                        scores_out.data_ptr(),
-                                        None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
-                                        L.stream_ptr(flat.device)), "ncf_rank_candidates")
+                                        scores_out.data_ptr(), *_ws_args(ws), L.stream_ptr(flat.device)),
+            "ncf_rank_candidates")
 
 
 def rank_candidates(model, users, cands, k):
@@ -910,15 +908,10 @@ def check_fold_examples(ex, item_num):
     labels = torch.as_tensor(ex.labels).to(torch.float32).view(-1)
     if ptr.numel() < 1 or items.numel() != labels.numel():
         raise ValueError("fold-in examples: ptr needs Q + 1 entries, items and labels equal length")
-    p = ptr.cpu()
-    if int(p[0]) != 0 or int(p[-1]) != items.numel() or (p.numel() > 1 and bool((p[1:] < p[:-1]).any())):
-        raise ValueError("fold-in examples: ptr must ascend from 0 to the number of examples")
-    if items.numel():
-        lo, hi = int(items.min()), int(items.max())
-        if lo < 0 or hi >= item_num:
-            raise IndexError("index out of range in self (item id)")
-        if float(labels.min()) < 0.0 or float(labels.max()) > 1.0 or bool(torch.isnan(labels).any()):
-            raise ValueError("fold-in examples: labels must lie in [0, 1]")
+    check_csr_ptr(ptr, items.numel(), "fold-in examples: ptr must ascend from 0 to the number of examples")
+    check_id_range((items, item_num, "item"))
+    if items.numel() and (float(labels.min()) < 0.0 or float(labels.max()) > 1.0 or bool(torch.isnan(labels).any())):
+        raise ValueError("fold-in examples: labels must lie in [0, 1]")
     return FoldExamples(ptr, items.to(torch.int32), labels)
 
 
@@ -933,21 +926,13 @@ def fold_opt(steps, lr, betas, eps, weight_decay, t0=0):
                         int(t0))
 
 
-@contextlib.contextmanager
 def _fold_generic():
     """Tests: ncf_fold_in through its generic path whatever the shape."""
-    L.check(L.hip().ncf_debug_set_fold_path(L.PATH_LAYERED), "ncf_debug_set_fold_path")
-    try:
-        yield
-    finally:
-        L.hip().ncf_debug_set_fold_path(0)
+    return _forced_path("fold")
 
 
 def fold_in_workspace(lay, n_users, n_examples, steps, owner, dev):
-    need = int(L.hip().ncf_fold_in_workspace_bytes(L.ctypes.byref(lay), int(n_users), int(n_examples), int(steps)))
-    if need < 0:
-        raise ValueError("ncf_fold_in_workspace_bytes failed")
-    return _ws(owner, "_ncf_fold_ws", need, dev)
+    return _serve_ws("fold_in", "_ncf_fold_ws", lay, owner, dev, n_users, n_examples, steps)
 
 
 def fold_in_into(flat, lay, ex, gmf, mlp, exp_avg, exp_avg_sq, opt, loss_out, grad_out, ws):
@@ -957,8 +942,7 @@ def fold_in_into(flat, lay, ex, gmf, mlp, exp_avg, exp_avg_sq, opt, loss_out, gr
     L.check(L.hip().ncf_fold_in(L.ctypes.byref(lay), flat.data_ptr(), ex.ptr.data_ptr(), L.ptr(ex.items) or None,
                                 L.ptr(ex.labels) or None, ex.ptr.numel() - 1, ex.items.numel(),
                                 gmf.data_ptr(), mlp.data_ptr(), L.ptr(exp_avg), L.ptr(exp_avg_sq),
-                                L.ctypes.byref(opt), L.ptr(loss_out), L.ptr(grad_out),
-                                None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
+                                L.ctypes.byref(opt), L.ptr(loss_out), L.ptr(grad_out), *_ws_args(ws),
                                 L.stream_ptr(flat.device)), "ncf_fold_in")
 
 

@@ -24,7 +24,6 @@ rtol 1e-5 at some step or a vector element beyond 1e-4 of the user's largest); t
 algorithmic FLOPs and bytes of a call computed from the shapes.  One JSON document (--out).
 """
 import argparse
-import json
 import os
 import sys
 
@@ -36,22 +35,13 @@ sys.path.append(os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 
 from ncf_amd import ops, synthetic  # noqa: E402
 from ncf_amd.models import NCF  # noqa: E402
+from serve_bench import alternate, emit, stats  # noqa: E402
 
 
-def stats(ms, q, steps):
-    a = np.sort(np.asarray(ms, dtype=np.float64))
-    med = float(np.median(a))
-    return {"median_ms": med, "min_ms": float(a[0]), "max_ms": float(a[-1]), "repeats": len(a),
-            "us_per_user_step": med * 1e3 / (q * steps), "users_per_s": q / (med * 1e-3)}
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
+def fold_stats(ms, q, steps):
+    """serve_bench.stats plus the per-user figures."""
+    s = stats(ms)
+    return dict(s, us_per_user_step=s["median_ms"] * 1e3 / (q * steps), users_per_s=q / (s["median_ms"] * 1e-3))
 
 
 def algorithmic_cost(f, nl, item_num, q, n_examples, steps):
@@ -185,28 +175,13 @@ def main(argv=None):
     fused_sorted = Fused(model, ex_sorted, gmf0, mlp0, args.steps, args.lr)
     base = TorchFold(model, ex, gmf0, mlp0, args.steps, args.lr, args.pad_budget)
 
-    def run(cand, repeats, warmup):
-        for _ in range(warmup):
-            cand.reset()
-            cand()
-        torch.cuda.synchronize()
-        out = []
-        for _ in range(repeats):
-            cand.reset()
-            torch.cuda.synchronize()
-            out.append(timed(cand))
-        return out
-
-    t_f, t_s = [], []
-    run(fused, 0, args.warmup)
-    run(fused_sorted, 0, args.warmup)
-    for _ in range(args.repeats):  # alternating
-        t_f += run(fused, 1, 0)
-        t_s += run(fused_sorted, 1, 0)
-    t_b = run(base, args.slow_repeats, 1)
+    # every candidate has a reset(): alternate() calls it before each call, outside the timing
+    times = alternate({"fused": fused, "sorted": fused_sorted}, args.warmup, args.repeats)
+    t_f, t_s = times["fused"], times["sorted"]
+    t_b = alternate({"torch": base}, 1, args.slow_repeats)["torch"]
     with ops._fold_generic():
         generic = Fused(model, ex, gmf0, mlp0, args.steps, args.lr)
-        t_g = run(generic, args.slow_repeats, 1)
+        t_g = alternate({"generic": generic}, 1, args.slow_repeats)["generic"]
     torch.cuda.synchronize()
 
     def gap(a, b):
@@ -225,11 +200,12 @@ def main(argv=None):
                   "folded_users": q, "examples": int(ex.items.numel()), "num_ng": args.num_ng, "steps": args.steps,
                   "examples_per_user": {"min": int(lengths.min()), "median": float(np.median(lengths)),
                                         "mean": float(lengths.mean()), "max": int(lengths.max())}},
-        "fused": dict(stats(t_f, q, args.steps), algorithmic=algorithmic_cost(f, nl, I, q, int(ex.items.numel()), args.steps)),
-        "fused_presorted": stats(t_s, q, args.steps),
-        "torch_rocm": dict(stats(t_b, q, args.steps), padded_batches=len(base.batches),
+        "fused": dict(fold_stats(t_f, q, args.steps),
+                      algorithmic=algorithmic_cost(f, nl, I, q, int(ex.items.numel()), args.steps)),
+        "fused_presorted": fold_stats(t_s, q, args.steps),
+        "torch_rocm": dict(fold_stats(t_b, q, args.steps), padded_batches=len(base.batches),
                            padded_examples=int(sum(b[1].numel() for b in base.batches))),
-        "generic": stats(t_g, q, args.steps),
+        "generic": fold_stats(t_g, q, args.steps),
         "agreement": {
             "largest_vector_magnitude": vec_scale,
             "fused_vs_torch_max_abs_vector": max(gap(fused.gmf, base.gmf.detach()), gap(fused.mlp, base.mlp.detach())),
@@ -249,11 +225,7 @@ def main(argv=None):
     }
     doc["torch_over_fused"] = doc["torch_rocm"]["median_ms"] / doc["fused"]["median_ms"]
     doc["generic_over_fused"] = doc["generic"]["median_ms"] / doc["fused"]["median_ms"]
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        json.dump(doc, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(doc))
+    emit(doc, args.out)
 
 
 if __name__ == "__main__":

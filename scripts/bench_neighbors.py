@@ -15,7 +15,6 @@ ratio, the fused call's workspace bytes, the baseline's peak allocation above th
 and how far the two results agree.  One JSON document (--out).
 """
 import argparse
-import json
 import os
 import sys
 
@@ -28,22 +27,7 @@ sys.path.append(os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 from ncf_amd import _lib as L  # noqa: E402
 from ncf_amd import ops  # noqa: E402
 from ncf_amd.models import NCF  # noqa: E402
-
-
-def stats(ms):
-    a = np.sort(np.asarray(ms, dtype=np.float64))
-    q1, med, q3 = np.percentile(a, [25, 50, 75])
-    return {"median_ms": float(med), "min_ms": float(a[0]), "max_ms": float(a[-1]), "iqr_ms": float(q3 - q1),
-            "repeats": len(a)}
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
+from serve_bench import alternate, emit, stats  # noqa: E402
 
 
 class Baseline:
@@ -99,23 +83,18 @@ def measure(I, f, nl, k, chunk_queries, warmup, repeats, dev):
     model = model.to(dev)
     fused = Fused(model, k)
     base = Baseline(model, k, chunk_queries)
-    for _ in range(warmup):
-        fused()
-        base()
-    torch.cuda.synchronize()
+    variants = {"fused": fused, "baseline": base}
+    alternate(variants, warmup, 0)
     before = torch.cuda.memory_allocated(dev)
     torch.cuda.reset_peak_memory_stats(dev)
     base()
     torch.cuda.synchronize()
     peak = int(torch.cuda.max_memory_allocated(dev) - before)
-    t_f, t_b = [], []
-    for _ in range(repeats):  # alternating
-        t_f.append(timed(fused))
-        t_b.append(timed(base))
+    times = alternate(variants, 0, repeats)
     fi, bi = fused.ids.cpu().numpy().astype(np.int64), base.ids.cpu().numpy()
     fs, bs = fused.scores.cpu().numpy(), base.scores.cpu().numpy()
     common = fi == bi
-    sf, sb = stats(t_f), stats(t_b)
+    sf, sb = stats(times["fused"]), stats(times["baseline"])
     d = f + (f << (nl - 1))
     return {
         "shape": {"item_num": I, "factor_num": f, "num_layers": nl, "side": "item", "space": "concat", "d": d,
@@ -144,11 +123,7 @@ def main(argv=None):
     doc = {"device": torch.cuda.get_device_name(0),
            "catalogues": [measure(I, 16, 3, args.top_k, args.chunk_queries, args.warmup, args.repeats, dev)
                           for I in args.items]}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        json.dump(doc, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(doc))
+    emit(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -23,7 +23,6 @@ of medians fused / materialised and fused / baseline, and how often the variants
 scores by slot).  One JSON document (--out).
 """
 import argparse
-import json
 import os
 import sys
 
@@ -34,24 +33,9 @@ sys.path.append(os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 
 from ncf_amd import ops  # noqa: E402
 from ncf_amd.models import NCF  # noqa: E402
+from serve_bench import alternate, emit, stats  # noqa: E402
 
 U, I, K = 6041, 3707, 10
-
-
-def stats(ms):
-    a = np.sort(np.asarray(ms, dtype=np.float64))
-    q1, med, q3 = np.percentile(a, [25, 50, 75])
-    return {"median_ms": float(med), "min_ms": float(a[0]), "max_ms": float(a[-1]), "iqr_ms": float(q3 - q1),
-            "repeats": len(a)}
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
 
 
 def workload(name, rng):
@@ -118,15 +102,8 @@ def main():
             base["scores"] = val
             base["items"] = cand[(ptr[:-1].unsqueeze(1) + j).clamp_(max=n_cand - 1)]
 
-        variants = {"fused": fused, "materialised": materialised, "baseline": baseline}
-        for fn in variants.values():
-            for _ in range(args.warmup):
-                fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in variants}
-        for _ in range(args.repeats):
-            for vname, fn in variants.items():
-                times[vname].append(timed(fn))
+        times = alternate({"fused": fused, "materialised": materialised, "baseline": baseline}, args.warmup,
+                          args.repeats)
         res = {k: stats(v) for k, v in times.items()}
         med = {k: v["median_ms"] for k, v in res.items()}
         res["candidates"] = n_cand
@@ -139,12 +116,7 @@ def main():
         out["rank"][name] = res
         del cand, users_rep, pad_index, rows, logits, padded
 
-    text = json.dumps(out, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

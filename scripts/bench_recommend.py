@@ -16,7 +16,6 @@ results agree.  For the record, NCF(64, 4) through ncf_recommend's materialised 
 time and workspace bytes.  One JSON document (--out).
 """
 import argparse
-import json
 import os
 import sys
 
@@ -28,6 +27,7 @@ sys.path.append(os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 from ncf_amd import _lib as L  # noqa: E402
 from ncf_amd import ops, synthetic  # noqa: E402
 from ncf_amd.models import NCF  # noqa: E402
+from serve_bench import alternate, emit, stats  # noqa: E402
 
 
 def algorithmic_cost(U, I, f, nl, q, k, nnz):
@@ -48,22 +48,6 @@ def algorithmic_cost(U, I, f, nl, q, k, nnz):
         "bytes": pairs * (16 + 4 * (2 * dm + 2 * f) + 8) + 8 * nnz + 8 * q * k,
     }
     return fused, baseline
-
-
-def stats(ms):
-    a = np.sort(np.asarray(ms, dtype=np.float64))
-    q1, med, q3 = np.percentile(a, [25, 50, 75])
-    return {"median_ms": float(med), "min_ms": float(a[0]), "max_ms": float(a[-1]), "iqr_ms": float(q3 - q1),
-            "repeats": len(a)}
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
 
 
 class Baseline:
@@ -136,21 +120,14 @@ def main(argv=None):
     model = NCF(U, I, f, nl, 0.0, "NeuMF-end").to(dev)
     fused = Fused(model, users, k, seen)
     base = Baseline(model, users, k, seen, args.chunk_users)
-    for _ in range(args.warmup):
-        fused()
-        base()
-    torch.cuda.synchronize()
-    t_f, t_b = [], []
-    for _ in range(args.repeats):  # alternating
-        t_f.append(timed(fused))
-        t_b.append(timed(base))
+    times = alternate({"fused": fused, "baseline": base}, args.warmup, args.repeats)
     fi, bi = fused.items.cpu().numpy().astype(np.int64), base.items.cpu().numpy()
     fs, bs = fused.scores.cpu().numpy(), base.scores.cpu().numpy()
     same_rows = float((fi == bi).all(axis=1).mean())
     same_sets = float(np.mean([set(a) == set(b) for a, b in zip(fi, bi)]))
     common = fi == bi
     cost_f, cost_b = algorithmic_cost(U, I, f, nl, U, k, nnz)
-    sf, sb = stats(t_f), stats(t_b)
+    sf, sb = stats(times["fused"]), stats(times["baseline"])
     doc = {
         "device": torch.cuda.get_device_name(0),
         "shape": {"user_num": U, "item_num": I, "factor_num": f, "num_layers": nl, "model_type": "NeuMF-end",
@@ -166,17 +143,10 @@ def main(argv=None):
     if args.record_repeats > 0:
         m2 = NCF(U, I, 64, 4, 0.0, "NeuMF-end").to(dev)
         rec = Fused(m2, users, k, seen)
-        for _ in range(2):
-            rec()
-        torch.cuda.synchronize()
-        doc["record_ncf_64_4_materialised"] = dict(stats([timed(rec) for _ in range(args.record_repeats)]),
+        doc["record_ncf_64_4_materialised"] = dict(stats(alternate({"rec": rec}, 2, args.record_repeats)["rec"]),
                                                    workspace_bytes=rec.ws_bytes,
                                                    path=int(L.supported("NeuMF-end", 64, 4)))
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        json.dump(doc, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(doc))
+    emit(doc, args.out)
 
 
 if __name__ == "__main__":

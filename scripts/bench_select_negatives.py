@@ -22,7 +22,6 @@ not overlapped.
 One JSON document (--out).
 """
 import argparse
-import json
 import os
 import sys
 
@@ -34,22 +33,7 @@ sys.path.append(os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 from ncf_amd import ops, synthetic  # noqa: E402
 from ncf_amd.engine import TrainEngine  # noqa: E402
 from ncf_amd.models import NCF  # noqa: E402
-
-
-def stats(ms):
-    a = np.sort(np.asarray(ms, dtype=np.float64))
-    q1, med, q3 = np.percentile(a, [25, 50, 75])
-    return {"median_ms": float(med), "min_ms": float(a[0]), "max_ms": float(a[-1]), "iqr_ms": float(q3 - q1),
-            "repeats": len(a)}
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
+from serve_bench import alternate, emit, stats  # noqa: E402
 
 
 def main():
@@ -99,15 +83,8 @@ def main():
             j = torch.argmax(logits.view(P, m), dim=1)
             base["items"] = cand.view(P, m).gather(1, j.unsqueeze(1)).squeeze(1)
 
-        variants = {"fused": fused, "materialised": materialised, "baseline": baseline}
-        for fn in variants.values():
-            for _ in range(args.warmup):
-                fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in variants}
-        for _ in range(args.repeats):
-            for name, fn in variants.items():
-                times[name].append(timed(fn))
+        times = alternate({"fused": fused, "materialised": materialised, "baseline": baseline}, args.warmup,
+                          args.repeats)
         res = {k: stats(v) for k, v in times.items()}
         med = {k: v["median_ms"] for k, v in res.items()}
         res["fused_over_materialised"] = med["fused"] / med["materialised"]
@@ -126,10 +103,8 @@ def main():
     eng = TrainEngine(model, lr=1e-3, loss="bpr")
     eng.set_epoch_stream(pairs, 2 * args.triples, checked=True)
     nb = eng.num_batches
-    eng.run(nb, use_graph=True)  # warm-up epoch (graph capture)
-    torch.cuda.synchronize()
-    epoch_ms = [timed(lambda: eng.run(nb, use_graph=True)) for _ in range(max(3, args.repeats // 2))]
-    ep = stats(epoch_ms)
+    # one warm-up epoch (graph capture)
+    ep = stats(alternate({"epoch": lambda: eng.run(nb, use_graph=True)}, 1, max(3, args.repeats // 2))["epoch"])
     ep["steps"] = int(nb)
     ep["triples_per_step"] = args.triples
     out["epoch_steps"] = ep
@@ -137,12 +112,7 @@ def main():
         sel = out["select"][f"m{m}"]["fused"]["median_ms"]
         out["select"][f"m{m}"]["selection_over_epoch_steps"] = sel / ep["median_ms"]
         out["select"][f"m{m}"]["share_of_epoch"] = sel / (sel + ep["median_ms"])
-    text = json.dumps(out, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -8,12 +8,19 @@ Per fused shape (every (type, f, layers) ncf_supported calls fused), at U = 50, 
   sel    ncf_select_negatives: n in {17, 1000} x m in {5, 40}, all three outputs
   fold   ncf_fold_in: 20 users with lists of 1 .. 40 examples, 5 steps; ug, um, both moments,
          loss_out and grad_out
-The same three for one shape without a fused kernel, NeuMF-end(6,3), through the
+  rank   ncf_rank_candidates: n_lists in {17, 1100} (17 < U: row-indexed projections, several
+         splits; 1100: one split, the user table) x k in {10, 128}, list lengths cycling
+         through 0, 1, 15, 16, 17, 80, 200 with repeated ids; all three outputs
+The same four for one shape without a fused kernel, NeuMF-end(6,3), through the
 materialised / generic paths, and one ncf_neighbors call (NeuMF-end(16,3): item side, concat
 space, cosine, k = 10).  Each of these is a fixed-order computation, so two runs of one
 library must agree bit for bit; --cmp checks that first (A against A2) and then B against A.
 One process per library (the library is chosen at import).
-usage: serve_bits.py --save DIR          (the hashed arrays as DIR/<shape>.npz; prints BITS lines)
+
+--cpu hashes instead what NCF.recommend, rank, hardest_negatives, similar_items and fold_in
+give on a CPU model (stock torch ops, no library) for GMF(8,1), MLP(8,2) and NeuMF-end(16,3),
+from the same seeds and inputs: the check of a change to the Python serving layer.
+usage: serve_bits.py [--cpu] --save DIR  (the hashed arrays as DIR/<shape>.npz; prints BITS lines)
        serve_bits.py --cmp DIR_A DIR_A2 DIR_B"""
 import hashlib
 import os
@@ -31,15 +38,22 @@ def shapes():
     return fused + [("NeuMF-end", 6, 3)]
 
 
-def outputs(mt, f, nl):
-    """name -> array of everything the three entry points give for this shape."""
+CPU_SHAPES = [("GMF", 8, 1), ("MLP", 8, 2), ("NeuMF-end", 16, 3)]
+RANK_LENGTHS = (0, 1, 15, 16, 17, 80, 200)
+
+
+def outputs(mt, f, nl, cpu=False):
+    """name -> array of everything the entry points (cpu: the NCF methods) give for this shape."""
     import numpy as np
     import torch
     from ncf_amd import ops
     from ncf_amd.models import NCF
-    dev = "cuda:0"
+    dev = "cpu" if cpu else "cuda:0"
     torch.manual_seed(11)
     m = NCF(U, I, f, nl, 0.0, mt).to(dev)
+    recommend = m.recommend if cpu else (lambda u, k, s: ops.recommend(m, u, k, s))
+    hardest = m.hardest_negatives if cpu else (lambda u, c: ops.select_negatives(m, u, c))
+    rank = m.rank if cpu else (lambda u, c, k: ops.rank_candidates(m, u, c, k))
     with torch.no_grad():  # spread tables: logits and ReLU masks are not degenerate
         for emb in (m.embed_user_GMF, m.embed_item_GMF, m.embed_user_MLP, m.embed_item_MLP):
             emb.weight.normal_(0.0, 0.3)
@@ -48,11 +62,11 @@ def outputs(mt, f, nl):
     su, si = np.nonzero(rng.random((U, I)) < 0.2)
     seen = ops.seen_csr(su, si, U, dev, I)
     for name, k, s in (("rec_k10_seen", 10, seen), ("rec_k80", I, None)):
-        it, sc = ops.recommend(m, torch.arange(U), k, s)
+        it, sc = recommend(torch.arange(U), k, s)
         out[name + "_items"], out[name + "_scores"] = it.cpu().numpy(), sc.cpu().numpy()
     for n in (17, 1000):
         for mm in (5, 40):
-            r = ops.select_negatives(m, rng.integers(0, U, n), rng.integers(0, I, (n, mm)))
+            r = hardest(rng.integers(0, U, n), rng.integers(0, I, (n, mm)))
             for key, v in zip(("items", "slots", "scores"), r):
                 out[f"sel_n{n}_m{mm}_{key}"] = v.cpu().numpy()
     lengths = np.linspace(1, 40, 20).round().astype(np.int64)
@@ -62,31 +76,45 @@ def outputs(mt, f, nl):
     dm = f << (nl - 1)
     gmf0 = torch.as_tensor(rng.normal(0, 0.3, (20, f)), dtype=torch.float32)
     mlp0 = torch.as_tensor(rng.normal(0, 0.3, (20, dm)), dtype=torch.float32)
-    grad = torch.zeros((20, f + dm), device=dev)
-    r = ops.fold_in(m, ex, gmf0, mlp0, 5, 0.05, (0.9, 0.999), 1e-8, 0.01, grad_out=grad)
-    torch.cuda.synchronize()
+    if cpu:
+        r = m.fold_in(ex, 5, 0.05, (0.9, 0.999), 1e-8, 0.01, init=(gmf0, mlp0))
+    else:
+        grad = torch.zeros((20, f + dm), device=dev)
+        r = ops.fold_in(m, ex, gmf0, mlp0, 5, 0.05, (0.9, 0.999), 1e-8, 0.01, grad_out=grad)
+        torch.cuda.synchronize()
+        out["fold_grad"] = grad.cpu().numpy()
     out.update(fold_ug=r.gmf.cpu().numpy(), fold_um=r.mlp.cpu().numpy(), fold_m=r.state.exp_avg.cpu().numpy(),
-               fold_v=r.state.exp_avg_sq.cpu().numpy(), fold_loss=r.loss.cpu().numpy(), fold_grad=grad.cpu().numpy())
-    if (mt, f, nl) == ("NeuMF-end", 16, 3):
-        ids, sc = ops.neighbors(m, "item", torch.arange(I), 10, "concat", "cosine")
+               fold_v=r.state.exp_avg_sq.cpu().numpy(), fold_loss=r.loss.cpu().numpy())
+    if cpu or (mt, f, nl) == ("NeuMF-end", 16, 3):
+        ids, sc = (m.similar_items(torch.arange(I), 10, "concat", "cosine") if cpu
+                   else ops.neighbors(m, "item", torch.arange(I), 10, "concat", "cosine"))
         out["nb_ids"], out["nb_scores"] = ids.cpu().numpy(), sc.cpu().numpy()
+    for n in (17, 1100):  # drawn after everything else: the arrays above keep their earlier inputs
+        lens = np.resize(RANK_LENGTHS, n)
+        lists = ops.CandidateLists(torch.as_tensor(np.concatenate([[0], np.cumsum(lens)])),
+                                   torch.as_tensor(rng.integers(0, I, int(lens.sum()))))
+        users = torch.as_tensor(rng.integers(0, U, n))
+        for k in (10, 128):
+            for key, v in zip(("items", "slots", "scores"), rank(users, lists, k)):
+                out[f"rank_n{n}_k{k}_{key}"] = v.cpu().numpy()
     assert all(np.isfinite(v[v > -np.inf]).all() for k, v in out.items() if v.dtype == np.float32)
     return out
 
 
-def save(dest):
+def save(dest, cpu=False):
     sys.path.insert(0, ROOT)
     import numpy as np
     os.makedirs(dest, exist_ok=True)
-    lib = os.environ.get("NCF_HIP_LIB", "") or "default"
-    for mt, f, nl in shapes():
-        out = outputs(mt, f, nl)
+    lib = "cpu" if cpu else os.environ.get("NCF_HIP_LIB", "") or "default"
+    for mt, f, nl in (CPU_SHAPES if cpu else shapes()):
+        out = outputs(mt, f, nl, cpu)
         name = f"{mt}_{f}_{nl}"
         np.savez(os.path.join(dest, name + ".npz"), **out)
         sha = lambda pre: hashlib.sha256(b"".join(out[k].tobytes() for k in sorted(out) if k.startswith(pre))
                                          ).hexdigest()[:16]
         nb = f" nb={sha('nb')}" if "nb_ids" in out else ""
-        print(f"BITS {name} lib={lib} rec={sha('rec')} sel={sha('sel')} fold={sha('fold')}{nb}", flush=True)
+        print(f"BITS {name} lib={lib} rec={sha('rec')} sel={sha('sel')} fold={sha('fold')} rank={sha('rank')}{nb}",
+              flush=True)
 
 
 def cmp(da, da2, db):
@@ -112,8 +140,9 @@ def cmp(da, da2, db):
 
 def main():
     args = sys.argv[1:]
-    if len(args) == 2 and args[0] == "--save":
-        return save(args[1])
+    cpu = args[:1] == ["--cpu"]
+    if len(args) == 2 + cpu and args[cpu] == "--save":
+        return save(args[-1], cpu)
     if len(args) == 4 and args[0] == "--cmp":
         return cmp(*args[1:])
     raise SystemExit(__doc__)

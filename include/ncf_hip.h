@@ -26,7 +26,8 @@ extern "C" {
  * ncf_neighbors_workspace_bytes, ncf_neighbors; ncf_fold_opt, ncf_fold_in_workspace_bytes,
  * ncf_fold_in, ncf_debug_set_fold_path; ncf_select_negatives_workspace_bytes,
  * ncf_select_negatives, ncf_debug_set_select_path; ncf_rank_candidates_workspace_bytes,
- * ncf_rank_candidates, ncf_debug_set_rank_path.
+ * ncf_rank_candidates, ncf_debug_set_rank_path; ncf_target_ranks_workspace_bytes,
+ * ncf_target_ranks, ncf_debug_set_target_path.
  * 20: full-catalogue top-K inference: ncf_recommend_workspace_bytes, ncf_recommend,
  * ncf_debug_set_recommend_path.
  * 19: NCF_LAYOUT_FACT_IN_ADAM (0x20) removed -- measured slower than the two launches it
@@ -874,6 +875,72 @@ int ncf_rank_candidates(const ncf_layout *lay, const float *params,
  * sizes) through the materialised path whatever the shape; 0 restores the choice from the
  * layout.  NCF_E_ARG otherwise. */
 int ncf_debug_set_rank_path(int path);
+
+/*
+ * Target ranks: the exact position of given items in a user's full-catalogue order -- what an
+ * evaluation needs of ncf_recommend without its top_k <= 128 limit: one integer per (user,
+ * held-out item), from which HR / Recall / NDCG at every K, MRR, MAP, AUC and the mean rank
+ * follow on the host.  Added within ABI 21 (NCF_ABI_VERSION is unchanged: the addition is
+ * purely additive); probe with dlsym before calling into a library that may predate it.  The
+ * reference has nothing of the kind.
+ *
+ * List q < n_lists belongs to user users[q] and holds the target item ids
+ * targets[tgt_ptr[q] .. tgt_ptr[q + 1]): tgt_ptr is a device array of n_lists + 1 ascending
+ * offsets with tgt_ptr[0] = 0 and tgt_ptr[n_lists] = n_tgt; the host never reads it (the launch
+ * geometry and the workspace size are functions of lay, n_lists and n_tgt).  A list may be
+ * empty, of any length, and may repeat ids.  For target t of user u, with z(u, i) =
+ * NCF.forward(u, i) in eval mode (models.py:97-118; dropout is never applied):
+ *   rank(u, t) = #{ j : j != t, j not in seen(u), z(u, j) > z(u, t) or (z(u, j) == z(u, t) and j < t) }
+ * -- the 0-based position t takes in ncf_recommend's order (score descending, item id
+ * ascending) among the user's eligible items, t itself counted as eligible whether or not it
+ * is in seen(u).  The user's other targets are ordinary competitors (counted if eligible,
+ * masked if seen); duplicate targets get equal ranks.  seen_ptr / seen_items are
+ * ncf_recommend's (indexed by user id, ascending and unique inside a user; both NULL: no
+ * exclusion).  ranks_out[e] and scores_out[e] (the target's own logit; scores_out may be NULL)
+ * belong to targets[e].  Every score is one fixed arithmetic sequence -- a pair's score has
+ * the bits ncf_recommend and ncf_rank_candidates give it -- and a rank is a sum of integers,
+ * so a list's result depends on that list alone: not on n_lists, on the list's position, on
+ * the other lists, on the tiling or on any split of the work.  Parameters are assumed finite.
+ * The caller range-checks the ids, as for ncf_forward.  Nothing is written outside entries
+ * [0, n_tgt); nothing is allocated or synchronised (the call can be captured).  n_lists == 0
+ * returns NCF_OK with nothing launched; a null required pointer, a negative count, one of
+ * seen_ptr / seen_items without the other or a workspace below
+ * ncf_target_ranks_workspace_bytes (-1 from that: bad argument) gives NCF_E_ARG; a shape
+ * ncf_supported refuses gives NCF_E_UNSUPPORTED.
+ *
+ * Two paths, chosen as ncf_recommend chooses (every shape ncf_supported accepts):
+ *   NCF_PATH_FUSED shapes with dm <= 64: ncf_recommend's prologue (Pi over the catalogue;
+ *     Pu and Ag over the call's rows, or over the user table when n_lists >= user_num); a
+ *     pre-pass that cuts every list into units of at most tb targets (tb = the power of two
+ *     in [16, 128] covering the mean list length), scores the targets 16 per MFMA tile and
+ *     leaves every unit sorted; and ncf_recommend's sweep with the list insert replaced by a
+ *     count: a workgroup of four waves owns a tile of 4 or 16 units and a range of 64-item
+ *     chunks, and every scored, unmasked item bumps the targets it beats -- by compare and
+ *     ballot in a unit of at most 4 targets, else by a binary search in the unit's sorted
+ *     keys and one LDS integer atomic on a histogram bucket.  The splits' counts meet in
+ *     ranks_out by integer atomics (the pre-pass zeroes it on every call).  Workspace:
+ *     (item_num + R) * max(16, dm) + R * max(16, f) floats, R = min(n_lists, user_num),
+ *     16 bytes per target and 20 bytes per unit (n_lists + n_tgt / tb of them), each array
+ *     rounded up to 256 bytes.
+ *   other shapes: list chunks of at most 131,072 (user, item) pairs -- the packed rows of the
+ *     chunk's users x every item are written, ncf_forward scores them -- then one wave per
+ *     list counts from its logits row with the same mask and order; the target's score is its
+ *     entry of that row.  Workspace: 12 bytes per pair of one chunk and
+ *     ncf_forward_workspace_bytes of it.
+ */
+int64_t ncf_target_ranks_workspace_bytes(const ncf_layout *lay, int64_t n_lists, int64_t n_tgt);
+int ncf_target_ranks(const ncf_layout *lay, const float *params,
+                     const int32_t *users   /* [n_lists] */,
+                     const int64_t *tgt_ptr /* [n_lists + 1], device, ascending, tgt_ptr[0] = 0 */,
+                     const int32_t *targets /* [n_tgt] item ids, list q = targets[tgt_ptr[q] .. tgt_ptr[q+1]) */,
+                     int64_t n_lists, int64_t n_tgt,
+                     const int64_t *seen_ptr /* [user_num + 1] or NULL */, const int32_t *seen_items,
+                     int32_t *ranks_out /* [n_tgt] */, float *scores_out /* [n_tgt] or NULL */,
+                     void *workspace, int64_t workspace_bytes, void *stream);
+/* Tests only: NCF_PATH_LAYERED sends later ncf_target_ranks calls (and their workspace sizes)
+ * through the materialised path whatever the shape; 0 restores the choice from the layout.
+ * NCF_E_ARG otherwise. */
+int ncf_debug_set_target_path(int path);
 
 /* Diagnostics only: ablation switches for the next ncf_train_step launches
  * (1 = skip embedding scatter-add, 2 = skip weight-gradient MFMAs).  Results are

@@ -158,6 +158,10 @@ _HIP_PROTOS = {
     "ncf_rank_candidates": (ctypes.c_int, [ctypes.POINTER(NcfLayout), c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
                                            ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "ncf_debug_set_rank_path": (ctypes.c_int, [ctypes.c_int]),
+    "ncf_target_ranks_workspace_bytes": (c_i64, [ctypes.POINTER(NcfLayout), c_i64, c_i64]),
+    "ncf_target_ranks": (ctypes.c_int, [ctypes.POINTER(NcfLayout), c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "ncf_debug_set_target_path": (ctypes.c_int, [ctypes.c_int]),
     "ncf_hr_ndcg": (ctypes.c_int, [c_vp, c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "ncf_fact_mode": (ctypes.c_int, [c_vp]),
     "ncf_reduce_rows": (ctypes.c_int, [c_vp]),

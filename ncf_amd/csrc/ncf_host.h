@@ -34,8 +34,8 @@ inline UserRows serve_user_rows(const ncf_layout* lay, int64_t n) {
     return n < lay->user_num ? UserRows{n, 1} : UserRows{(int64_t)lay->user_num, 0};
 }
 
-// Materialised paths (ncf_recommend, ncf_select_negatives, ncf_rank_candidates): packed rows,
-// their logits and ncf_forward's own workspace for chunks of at most `pairs` (user, item)
+// Materialised paths (ncf_recommend, ncf_select_negatives, ncf_rank_candidates,
+// ncf_target_ranks): packed rows, their logits and ncf_forward's own workspace for chunks of at most `pairs` (user, item)
 // pairs.  (ws_align is in ncf_common.h, the fused paths' proj_ws in ncf_tower_tile.h.)
 struct MatWs {
     int64_t rows, logits, fwd, fwd_bytes, total;

@@ -51,32 +51,6 @@ struct RcArgs {
     int upw;          // users per wave
 };
 
-// First position p in [lo, hi) with seen_items[p] >= item (wave-uniform).
-__device__ __forceinline__ int64_t rc_lower_bound(const int32_t* __restrict__ seen_items, int64_t lo, int64_t hi,
-                                                  int item) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (seen_items[mid] < item) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// Seen mask of the 64 items [c0, c0 + 64) of a user whose cursor *cur points at the first
-// list entry >= c0: bit j = item c0 + j is in the list.  The list is ascending and unique,
-// so at most 64 entries fall in the chunk and one load per lane covers them; every access
-// is bounded by hi = seen_ptr[u + 1].  scr: 64 ints of per-wave LDS.
-__device__ __forceinline__ unsigned long long rc_seen_mask(const int32_t* __restrict__ seen_items, int64_t* cur,
-                                                           int64_t hi, int c0, volatile int* scr, int lane) {
-    const int64_t p = *cur + lane;
-    const int v = p < hi ? seen_items[p] : RC_IDMAX;
-    const bool below = p < hi && v < c0 + RC_CH;
-    scr[lane] = 0;
-    if (below && v >= c0) scr[v - c0] = 1;
-    const unsigned long long mask = __ballot(scr[lane] != 0);
-    *cur += __popcll(__ballot(below));
-    return mask;
-}
-
 template <int F, int L, int MODE>
 __global__ __launch_bounds__(RC_WAVES * 64) void rc_kernel(RcArgs a) {
     using C = RcShape<F, L, MODE>;
@@ -251,28 +225,6 @@ struct RcKernel {
     static constexpr auto kernel = &rc_kernel<F, L, MODE>;
 };
 static const TileEntry* rc_fused(const ncf_layout* lay) { return tile_fused<RcKernel>(lay, g_rc_path); }
-
-// Launch shape of the fused kernel from the query size and the catalogue: 16-user tiles
-// from 256 queried users up (4-user tiles below), and as many item splits as bring the
-// grid to about four workgroups per compute unit.
-struct RcGeo {
-    int upw, nsplit, cps;
-    int64_t tiles;
-};
-static RcGeo rc_geometry(int64_t nq, int I) {
-    RcGeo G;
-    G.upw = nq >= 256 ? 4 : 1;
-    const int UT = RC_WAVES * G.upw;
-    G.tiles = (nq + UT - 1) / UT;
-    const int64_t nchunks = ((int64_t)I + RC_CH - 1) / RC_CH;
-    int64_t want = (1024 + G.tiles - 1) / G.tiles;
-    if (want > nchunks) want = nchunks;
-    if (want > 1024) want = 1024;
-    if (want < 1) want = 1;
-    G.cps = (int)((nchunks + want - 1) / want);
-    G.nsplit = (int)((nchunks + G.cps - 1) / G.cps);
-    return G;
-}
 
 static int64_t rc_lds_bytes(const TileEntry* e, const RcGeo& G, int K) {
     const int UT = RC_WAVES * G.upw;

@@ -1,6 +1,7 @@
 // The in-register MFMA tower tile shared by the serving entry points -- ncf_recommend.hip
-// (full-catalogue top-K), ncf_select.hip (hardest negatives) and ncf_fold.hip (fold-in of
-// unseen users): the list of fused shapes and the table built from it, the padded shape
+// (full-catalogue top-K), ncf_select.hip (hardest negatives), ncf_rank.hip (candidate
+// ranking), ncf_target.hip (target ranks) and ncf_fold.hip (fold-in of unseen users): the
+// list of fused shapes and the table built from it, the padded shape
 // constants, the layer-0 projection prologue (its kernel, its place in a workspace and its
 // launch: rc_proj_kernel, proj_ws, launch_proj), the staging of the tower into LDS, and the
 // pair score (h0, the layer ladder, the predict and GMF dots, the logit).  ncf_train.hip
@@ -244,6 +245,57 @@ __device__ __forceinline__ float tile_logit(float part, float bp) {
     part += shfl_xor(part, 16);
     part += shfl_xor(part, 32);
     return part + bp;
+}
+
+// ---------------------------------------------------------------------------
+// The catalogue sweep of ncf_recommend and ncf_target_ranks: the seen mask of a 64-item chunk
+// and the launch shape.
+// First position p in [lo, hi) with seen_items[p] >= item (wave-uniform).
+__device__ __forceinline__ int64_t rc_lower_bound(const int32_t* __restrict__ seen_items, int64_t lo, int64_t hi,
+                                                  int item) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (seen_items[mid] < item) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// Seen mask of the 64 items [c0, c0 + 64) of a user whose cursor *cur points at the first
+// list entry >= c0: bit j = item c0 + j is in the list.  The list is ascending and unique,
+// so at most 64 entries fall in the chunk and one load per lane covers them; every access
+// is bounded by hi = seen_ptr[u + 1].  scr: 64 ints of per-wave LDS.
+__device__ __forceinline__ unsigned long long rc_seen_mask(const int32_t* __restrict__ seen_items, int64_t* cur,
+                                                           int64_t hi, int c0, volatile int* scr, int lane) {
+    const int64_t p = *cur + lane;
+    const int v = p < hi ? seen_items[p] : RC_IDMAX;
+    const bool below = p < hi && v < c0 + RC_CH;
+    scr[lane] = 0;
+    if (below && v >= c0) scr[v - c0] = 1;
+    const unsigned long long mask = __ballot(scr[lane] != 0);
+    *cur += __popcll(__ballot(below));
+    return mask;
+}
+
+// Launch shape of the fused kernel from the query size and the catalogue: 16-user tiles
+// from 256 queried users up (4-user tiles below), and as many item splits as bring the
+// grid to about four workgroups per compute unit.
+struct RcGeo {
+    int upw, nsplit, cps;
+    int64_t tiles;
+};
+inline RcGeo rc_geometry(int64_t nq, int I) {
+    RcGeo G;
+    G.upw = nq >= 256 ? 4 : 1;
+    const int UT = RC_WAVES * G.upw;
+    G.tiles = (nq + UT - 1) / UT;
+    const int64_t nchunks = ((int64_t)I + RC_CH - 1) / RC_CH;
+    int64_t want = (1024 + G.tiles - 1) / G.tiles;
+    if (want > nchunks) want = nchunks;
+    if (want > 1024) want = 1024;
+    if (want < 1) want = 1;
+    G.cps = (int)((nchunks + want - 1) / want);
+    G.nsplit = (int)((nchunks + G.cps - 1) / G.cps);
+    return G;
 }
 
 // ---------------------------------------------------------------------------

@@ -139,3 +139,81 @@ def full_rank_metrics(model, users, gt_items, top_k, exclude=None):
         return [], []
     items, _ = model.recommend(torch.as_tensor(users.astype(np.int64)), top_k, exclude)
     return hr_ndcg_from_topk(items.cpu().numpy(), gt)
+
+
+def _host(x):
+    return np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x)
+
+
+def rank_report(ranks, ptr, eligible, ks=(1, 5, 10, 20, 50, 100)):
+    """Ranking metrics from exact full-catalogue ranks (``NCF.target_ranks``): pure NumPy.
+
+    ``ranks``: the 0-based ranks of every held-out item, flat or shaped, in the order ``ptr``
+    (int64 [n + 1]) cuts into the n users' lists; ``eligible`` [n]: the number of items each
+    user's ranks are out of.  For a user with P >= 1 held-out items at sorted ranks
+    r_0 < ... < r_{P-1} among E eligible items:
+      hr@k = any r < k;  recall@k = #{r < k} / P;  precision@k = #{r < k} / k;
+      ndcg@k = sum_{r < k} 1 / log2(r + 2)  over  sum_{j < min(P, k)} 1 / log2(j + 2);
+      mrr = 1 / (r_0 + 1);  map (average precision) = mean_j (j + 1) / (r_j + 1);
+      auc = 1 - sum_j (r_j - j) / (P (E - P)), NaN when E = P;  mean_rank = mean_j r_j.
+    The formulas assume a user's held-out items are distinct and not among the items the
+    ranks excluded (``exclude`` of ``target_ranks``): then a user's ranks are distinct.  Two
+    equal ranks in one list mean a duplicate target: ValueError.
+
+    Returns ``{"users": the users with P >= 1, "mean": {name: mean over those users},
+    "per_user": {name: float64 [n]}}`` with names ``hr@k`` ... for every k of ``ks``, ``mrr``,
+    ``map``, ``auc``, ``mean_rank``; a user without held-out items has NaN throughout and is
+    left out of the means, as is a NaN auc."""
+    r = _host(ranks).reshape(-1).astype(np.int64)
+    ptr = _host(ptr).reshape(-1).astype(np.int64)
+    n = ptr.size - 1
+    E = _host(eligible).reshape(-1).astype(np.float64)
+    if n < 0 or E.size != n or ptr[0] != 0 or ptr[-1] != r.size or (np.diff(ptr) < 0).any():
+        raise ValueError("rank_report: ptr [n + 1] must ascend from 0 to len(ranks), eligible [n]")
+    ks = [int(k) for k in ks]
+    if any(k < 1 for k in ks):
+        raise ValueError("rank_report: every k must be at least 1")
+    P = np.diff(ptr)
+    owner = np.repeat(np.arange(n), P)
+    r = r[np.lexsort((r, owner))]  # ascending inside every user; owner is already ascending
+    if ((r[1:] == r[:-1]) & (owner[1:] == owner[:-1])).any():
+        raise ValueError("rank_report: a user has two equal ranks (duplicate targets)")
+    j = np.arange(r.size) - ptr[owner]  # position among the user's sorted ranks
+    has = P >= 1
+    Pf = np.where(has, P, 1).astype(np.float64)
+    nan = np.where(has, 0.0, np.nan)  # added to every per-user value: NaN for a user without targets
+
+    def per_user(w):
+        return np.bincount(owner, weights=w, minlength=n)
+
+    gain = 1.0 / np.log2(r + 2.0)
+    ideal = np.concatenate([[0.0], np.cumsum(1.0 / np.log2(np.arange(max(int(P.max()) if n else 0, 1)) + 2.0))])
+    out = {}
+    for k in ks:
+        hit = (r < k).astype(np.float64)
+        hits = per_user(hit)
+        out[f"hr@{k}"] = (hits > 0).astype(np.float64) + nan
+        out[f"recall@{k}"] = hits / Pf + nan
+        out[f"precision@{k}"] = hits / k + nan
+        out[f"ndcg@{k}"] = per_user(hit * gain) / np.where(has, ideal[np.minimum(P, k)], 1.0) + nan
+    first = np.full(n, np.nan)
+    first[has] = r[ptr[:-1][has]]
+    out["mrr"] = 1.0 / (first + 1.0)
+    out["map"] = per_user((j + 1.0) / (r + 1.0)) / Pf + nan
+    room = Pf * (E - P)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["auc"] = np.where(room > 0, 1.0 - per_user((r - j).astype(np.float64)) / room, np.nan) + nan
+    out["mean_rank"] = per_user(r.astype(np.float64)) / Pf + nan
+    mean = {}
+    for name, v in out.items():
+        ok = ~np.isnan(v)
+        mean[name] = float(v[ok].mean()) if ok.any() else float("nan")
+    return {"users": int(has.sum()), "mean": mean, "per_user": out}
+
+
+def full_rank_report(model, users, targets, ks=(1, 5, 10, 20, 50, 100), exclude=None):
+    """``rank_report`` of ``model.target_ranks(users, targets, exclude)``: every ranking metric
+    at every K over the whole catalogue, for any number of held-out items per user
+    (``targets`` as ``NCF.target_ranks`` takes them; ``exclude`` usually the training positives)."""
+    r = model.target_ranks(users, targets, exclude)
+    return rank_report(r.ranks, r.ptr, r.eligible, ks)

@@ -829,6 +829,75 @@ def rank_candidates(model, users, cands, k):
 
 
 # ---------------------------------------------------------------------------
+# target ranks: exact full-catalogue positions of given items (ncf_target_ranks; added within ABI 21)
+class TargetRanks(collections.namedtuple("TargetRanks", "ranks scores ptr eligible")):
+    """Result of NCF.target_ranks: per target its 0-based position in the user's full-catalogue
+    order and its logit (flat, in the order of the targets, or shaped like an array input);
+    ptr int64 [n + 1] cuts the flat order into the n lists; eligible int64 [n] is what each
+    list's ranks are out of: item_num minus the user's seen items."""
+    __slots__ = ()
+
+
+def check_target_args(users, lists, user_num, item_num):
+    """(n_lists, n_tgt) of users [n] and a CandidateLists of targets: check_rank_args' errors
+    (two host reads)."""
+    try:
+        return check_rank_args(users, lists, user_num, item_num)
+    except ValueError as e:
+        raise ValueError(str(e).replace("rank:", "target_ranks:")) from None
+
+
+def eligible_counts(users, seen, item_num):
+    """int64 [n]: item_num - len(seen(users[q])), computed where `users` lives (no host read)."""
+    u = users.to(torch.int64)
+    if seen is None:
+        return torch.full_like(u, int(item_num))
+    return int(item_num) - (seen.ptr[u + 1] - seen.ptr[u])
+
+
+def _target_materialised():
+    """Tests: ncf_target_ranks through its materialised path whatever the shape."""
+    return _forced_path("target")
+
+
+def target_ranks_workspace(lay, n_lists, n_tgt, owner, dev):
+    return _serve_ws("target_ranks", "_ncf_target_ws", lay, owner, dev, n_lists, n_tgt)
+
+
+def target_ranks_into(flat, lay, users_i32, ptr_i64, tgt_i32, seen, ranks_out, scores_out, ws):
+    """One ncf_target_ranks call on the current stream into preallocated tensors (capturable:
+    nothing is allocated or synchronised).  users_i32 [n], ptr_i64 [n + 1], tgt_i32 [ptr[n]];
+    ranks_out int32 and scores_out float32 [ptr[n]]; scores_out may be None."""
+    L.check(L.hip().ncf_target_ranks(L.ctypes.byref(lay), flat.data_ptr(), users_i32.data_ptr(),
+                                     ptr_i64.data_ptr(), tgt_i32.data_ptr(), users_i32.numel(), tgt_i32.numel(),
+                                     None if seen is None else seen.ptr.data_ptr(),
+                                     None if seen is None else seen.items.data_ptr(),
+                                     ranks_out.data_ptr(), L.ptr(scores_out), *_ws_args(ws),
+                                     L.stream_ptr(flat.device)),
+            "ncf_target_ranks")
+
+
+def target_ranks(model, users, targets, seen=None):
+    """TargetRanks (ranks int32 [E], scores float32 [E], ptr, eligible) of a HIP-resident model:
+    for every target of every list its position in the user's order over the whole catalogue
+    (score descending, item id ascending), `seen` (a SeenCSR on the device) left out."""
+    flat, lay = ensure_flat(model)
+    dev = flat.device
+    u = _as_i32(users, dev)
+    lists = candidate_lists(targets, n_users=u.numel(), device=dev)
+    ptr = torch.as_tensor(lists.ptr, device=dev).contiguous()
+    n, n_tgt = check_target_args(u, CandidateLists(ptr, lists.items), model.user_num, model.item_num)
+    t = _as_i32(lists.items, dev)
+    ranks = torch.empty(n_tgt, dtype=torch.int32, device=dev)
+    scores = torch.empty(n_tgt, dtype=torch.float32, device=dev)
+    eligible = eligible_counts(u, seen, model.item_num)
+    if n and n_tgt:
+        ws = target_ranks_workspace(lay, n, n_tgt, model, dev)
+        target_ranks_into(flat, lay, u, ptr, t, seen, ranks, scores, ws)
+    return TargetRanks(ranks, scores, ptr, eligible)
+
+
+# ---------------------------------------------------------------------------
 # fold-in: vectors for unseen users from their interaction lists (ncf_fold_in; added within ABI 21)
 class FoldExamples(collections.namedtuple("FoldExamples", "ptr items labels")):
     """Examples of Q folded users: ptr int64 [Q + 1], items int32 [E], labels float32 [E]

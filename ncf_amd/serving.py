@@ -1,5 +1,5 @@
 """What a trained NCF serves beyond ``forward``: full-catalogue recommendation, hardest negatives,
-candidate ranking, nearest neighbours over the embedding tables, fold-in of unseen users.
+candidate ranking, exact ranks of given items, nearest neighbours over the embedding tables, fold-in of unseen users.
 ``ServingMixin`` is a base of ``models.NCF``.  On a HIP device every method is one entry point of
 libncf_hip.so (``ncf_amd.ops``; no fallback to ATen ops); on a CPU device, stock torch ops.
 """
@@ -180,6 +180,92 @@ class ServingMixin:
             out_j[b:e], out_s[b:e] = _topk_pad(s, ln, k)
             out_i[b:e] = torch.where(out_j[b:e] < 0, out_j[b:e], ids.gather(1, out_j[b:e].clamp(min=0)))
         return ops.Ranked(out_i, out_j, out_s)
+
+    # -------------------------------------------------------------- target ranks
+    def target_ranks(self, users, targets, exclude=None):
+        """The exact position of given items in each queried user's order over the whole
+        catalogue -- what an evaluation needs, without ``recommend``'s k <= 128:
+        ``ops.TargetRanks(ranks int64, scores float32, ptr int64 [n + 1], eligible int64 [n])``
+        on the model's device.  ``users`` [n]; ``targets`` is an ``ops.CandidateLists`` or a
+        sequence of per-user id sequences (ragged: ``ranks`` / ``scores`` come back flat, in
+        the order of the targets, list q at ``ptr[q] .. ptr[q + 1]``), a 2-D ``[n, m]`` array
+        (``ranks`` / ``scores`` are ``[n, m]``) or a 1-D ``[n]`` array: ONE TARGET PER USER
+        (``ranks`` / ``scores`` are ``[n]``).  The 1-D form deliberately differs from
+        ``rank()``, where a 1-D array is one list shared by every user: an evaluation holds
+        out an item per user, a re-ranker shares a shelf.
+
+        ``rank`` of target t of user u is the number of items j != t outside ``exclude`` with
+        ``forward(u, j)`` above ``forward(u, t)``, or equal to it with j < t (eval mode:
+        dropout never applies): the 0-based position t takes in ``recommend``'s order.  t
+        itself counts as eligible whether or not ``exclude`` holds it; the user's other
+        targets are ordinary competitors; duplicate targets get equal ranks; a list may be
+        empty.  ``scores`` is the target's own logit.  ``eligible[q]`` is ``item_num`` minus
+        the items ``exclude`` holds for ``users[q]``: what the list's ranks are out of.
+        ``exclude`` is as in ``recommend``.  A list's result depends on that list alone.
+        IndexError for an id outside the tables; ValueError for a bad shape, a non-monotone
+        ``ptr`` or a ``users`` / ``targets`` length mismatch.  ``metrics.rank_report`` turns
+        the result into HR / Recall / NDCG at any K, MRR, MAP, AUC and the mean rank.
+
+        On a HIP device this is ``ncf_target_ranks`` (the fused score-and-count kernel); a
+        CPU model runs the same contract with stock torch ops."""
+        dev = self.embed_user_GMF.weight.device
+        u = torch.as_tensor(users)
+        shape = None
+        ragged = isinstance(targets, (list, tuple)) and any(
+            isinstance(x, (list, tuple)) or getattr(x, "ndim", 0) > 0 for x in targets)
+        if not isinstance(targets, ops.CandidateLists) and not ragged:
+            t = torch.as_tensor(targets)
+            if t.dim() == 1:
+                if u.dim() != 1 or t.numel() != u.numel():
+                    raise ValueError("target_ranks: a 1-D targets array holds one target per user: users [n], "
+                                     "targets [n]")
+                t = t.reshape(-1, 1)
+            elif t.dim() != 2:
+                raise ValueError("target_ranks: targets must be a CandidateLists, a sequence of lists, a 2-D [n, m] "
+                                 "array or a 1-D [n] array (one target per user)")
+            shape = tuple(torch.as_tensor(targets).shape)
+            targets = t
+        lists = ops.candidate_lists(targets, n_users=u.numel(), device=dev)
+        seen = ops.as_seen(exclude, self, dev)
+        if dev.type == "cuda":
+            r = ops.target_ranks(self, u, lists, seen)
+            r = r._replace(ranks=r.ranks.to(torch.int64))
+        else:
+            r = self._target_ranks_cpu(u, lists, seen)
+        if shape is not None:
+            r = r._replace(ranks=r.ranks.view(shape), scores=r.scores.view(shape))
+        return r
+
+    @torch.no_grad()
+    def _target_ranks_cpu(self, users, lists, seen, chunk_pairs=1 << 20):
+        u = users.to(torch.int64)
+        ptr = torch.as_tensor(lists.ptr)
+        n, n_tgt = ops.check_target_args(u, ops.CandidateLists(ptr, lists.items), self.user_num, self.item_num)
+        t = lists.items.to(torch.int64)
+        n_items = self.item_num
+        ranks = torch.zeros(n_tgt, dtype=torch.int64)
+        scores = torch.zeros(n_tgt, dtype=torch.float32)
+        owner = torch.repeat_interleave(torch.arange(n), ptr[1:] - ptr[:-1])  # the list of every target
+        all_items = torch.arange(n_items, dtype=torch.int64)
+        step = max(1, chunk_pairs // n_items)
+        for b in range(0, n_tgt, step):
+            tt = t[b:b + step].unsqueeze(1)
+            here, row = torch.unique(owner[b:b + step], return_inverse=True)  # at most `step` lists are scored
+            uc = u[here]
+            c = uc.numel()
+            s = self._logits_eval(uc.repeat_interleave(n_items), all_items.repeat(c)).view(c, n_items)
+            free = torch.ones((c, n_items), dtype=torch.bool)
+            if seen is not None:
+                lo, hi = seen.ptr[uc], seen.ptr[uc + 1]
+                for r in range(c):
+                    free[r, seen.items[int(lo[r]):int(hi[r])].to(torch.int64)] = False
+            z = s[row]
+            zt = z.gather(1, tt)
+            # the target itself is never ahead of itself: equal score, equal id
+            ahead = (z > zt) | ((z == zt) & (all_items.unsqueeze(0) < tt))
+            ranks[b:b + step] = (ahead & free[row]).sum(1)
+            scores[b:b + step] = zt[:, 0]
+        return ops.TargetRanks(ranks, scores, ptr, ops.eligible_counts(u, seen, n_items))
 
     # ---------------------------------------------------------------- neighbours
     def similar_items(self, items, k=10, space=None, metric="cosine", exclude_self=True):

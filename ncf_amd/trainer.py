@@ -235,6 +235,28 @@ class Trainer:
                                           int(self.model.item_num))
         return full_rank_metrics(self.model, u[::bs], i[::bs], k, self._seen)
 
+    def evaluate_ranks(self):
+        """The exact full-catalogue rank of every test user's held-out item
+        (``NCF.target_ranks``): an ``ops.TargetRanks`` with one entry per test user, over the
+        users, items and exclusions of ``evaluate_full`` -- ``ranks < k`` is its HR@k and
+        ``1 / log2(ranks + 2)`` its NDCG for every k, not only k <= 128;
+        ``ncf_amd.metrics.rank_report`` gives the other metrics.  Draws nothing from the
+        torch generator."""
+        # evaluate_full's own preparation, kept apart from it
+        if self._test is None:
+            state = torch.get_rng_state()
+            self._test_arrays()
+            torch.set_rng_state(state)
+        u, i, bs = self._test_arrays()
+        if getattr(self, "_seen", None) is None:
+            mat = getattr(self.ds, "train_mat", None)
+            if mat is not None and hasattr(mat, "keys") and hasattr(mat, "shape"):
+                self._seen = ops.seen_csr(mat, None, int(self.model.user_num), self.device, int(self.model.item_num))
+            else:
+                self._seen = ops.seen_csr(self.ds._ps_u, self.ds._ps_i, int(self.model.user_num), self.device,
+                                          int(self.model.item_num))
+        return self.model.target_ranks(u[::bs].astype(np.int64), i[::bs].astype(np.int64), self._seen)
+
     def train_epoch(self):
         rows = self._epoch_stream()
         self.engine.set_epoch_stream(rows, self._batch_rows, checked=True)  # ids checked on the host

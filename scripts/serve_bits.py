@@ -11,14 +11,15 @@ Per fused shape (every (type, f, layers) ncf_supported calls fused), at U = 50, 
   rank   ncf_rank_candidates: n_lists in {17, 1100} (17 < U: row-indexed projections, several
          splits; 1100: one split, the user table) x k in {10, 128}, list lengths cycling
          through 0, 1, 15, 16, 17, 80, 200 with repeated ids; all three outputs
-The same four for one shape without a fused kernel, NeuMF-end(6,3), through the
+  tgt    ncf_target_ranks: the same lists as targets, with the seen CSR and without (ranks, scores)
+The same five for one shape without a fused kernel, NeuMF-end(6,3), through the
 materialised / generic paths, and one ncf_neighbors call (NeuMF-end(16,3): item side, concat
 space, cosine, k = 10).  Each of these is a fixed-order computation, so two runs of one
 library must agree bit for bit; --cmp checks that first (A against A2) and then B against A.
 One process per library (the library is chosen at import).
 
---cpu hashes instead what NCF.recommend, rank, hardest_negatives, similar_items and fold_in
-give on a CPU model (stock torch ops, no library) for GMF(8,1), MLP(8,2) and NeuMF-end(16,3),
+--cpu hashes instead what NCF.recommend, rank, target_ranks, hardest_negatives, similar_items and
+fold_in give on a CPU model (stock torch ops, no library) for GMF(8,1), MLP(8,2) and NeuMF-end(16,3),
 from the same seeds and inputs: the check of a change to the Python serving layer.
 usage: serve_bits.py [--cpu] --save DIR  (the hashed arrays as DIR/<shape>.npz; prints BITS lines)
        serve_bits.py --cmp DIR_A DIR_A2 DIR_B"""
@@ -54,6 +55,7 @@ def outputs(mt, f, nl, cpu=False):
     recommend = m.recommend if cpu else (lambda u, k, s: ops.recommend(m, u, k, s))
     hardest = m.hardest_negatives if cpu else (lambda u, c: ops.select_negatives(m, u, c))
     rank = m.rank if cpu else (lambda u, c, k: ops.rank_candidates(m, u, c, k))
+    target_ranks = m.target_ranks if cpu else (lambda u, t, s: ops.target_ranks(m, u, t, s))
     with torch.no_grad():  # spread tables: logits and ReLU masks are not degenerate
         for emb in (m.embed_user_GMF, m.embed_item_GMF, m.embed_user_MLP, m.embed_item_MLP):
             emb.weight.normal_(0.0, 0.3)
@@ -97,6 +99,9 @@ def outputs(mt, f, nl, cpu=False):
         for k in (10, 128):
             for key, v in zip(("items", "slots", "scores"), rank(users, lists, k)):
                 out[f"rank_n{n}_k{k}_{key}"] = v.cpu().numpy()
+        for tag, s in (("seen", seen), ("all", None)):
+            r = target_ranks(users, lists, s)
+            out[f"tgt_n{n}_{tag}_ranks"], out[f"tgt_n{n}_{tag}_scores"] = r.ranks.cpu().numpy(), r.scores.cpu().numpy()
     assert all(np.isfinite(v[v > -np.inf]).all() for k, v in out.items() if v.dtype == np.float32)
     return out
 
@@ -113,8 +118,8 @@ def save(dest, cpu=False):
         sha = lambda pre: hashlib.sha256(b"".join(out[k].tobytes() for k in sorted(out) if k.startswith(pre))
                                          ).hexdigest()[:16]
         nb = f" nb={sha('nb')}" if "nb_ids" in out else ""
-        print(f"BITS {name} lib={lib} rec={sha('rec')} sel={sha('sel')} fold={sha('fold')} rank={sha('rank')}{nb}",
-              flush=True)
+        print(f"BITS {name} lib={lib} rec={sha('rec')} sel={sha('sel')} fold={sha('fold')} rank={sha('rank')} "
+              f"tgt={sha('tgt')}{nb}", flush=True)
 
 
 def cmp(da, da2, db):

@@ -351,11 +351,16 @@ class DeviceDistillPlan:
             self.active_extra = [True] * 4 + [False] * (2 * student.num_layers + 2)
 
     def teacher_logits(self, rows):
+        """The teacher's logit of every row of the stream into self.tlog.  Returns whether
+        tlog was replaced (another stream length): launches captured before then hold the
+        old buffer's pointer."""
         n = rows.numel()
-        if self.tlog is None or self.tlog.numel() != n:
+        replaced = self.tlog is None or self.tlog.numel() != n
+        if replaced:
             self.tlog = torch.empty(n, dtype=torch.float32, device=rows.device)
         with torch.no_grad():
             ops.forward_logits(self.t_flat, self.t_lay, rows, out=self.tlog, ws_owner=self.teacher)
+        return replaced
 
     def launch(self, eng, st):
         lib = L.hip()

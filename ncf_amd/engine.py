@@ -341,8 +341,10 @@ class TrainEngine:
                                            L.stream_ptr(self.device)), "ncf_user_order")
         if self.distill is not None:
             # the frozen teacher's logit for every row of the epoch stream (one
-            # forward launch per epoch instead of one no_grad forward per step)
-            self.distill.teacher_logits(rows)
+            # forward launch per epoch instead of one no_grad forward per step); a new
+            # logit buffer (another stream length) invalidates every captured step
+            if self.distill.teacher_logits(rows):
+                self._drop_graphs()
 
     def _check_stream_agreement(self, rows):
         """world > 1: every rank must train on the same epoch stream (same seeds, and
